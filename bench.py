@@ -21,10 +21,20 @@ fixed-capacity all-to-all of projected splats and of their gradients).  ``value`
 bytes each rank exchanges per step; ``job`` holds the world size, every rank's device and the RCCL version as the
 process group reports them.
 
-N = 1: ``render_gaussians(...).image.sum().backward()`` per step (the frame executor), plus the same step replayed from a
-HIP graph (``graph_ms_per_step``, timed in a child process) and the tile 8 / 16 / 32 sweep BASELINE.json names.
+N = 1: ``render_gaussians(...).image.sum().backward()`` per step (the frame executor).
 
-Prints ONE JSON line on rank 0 (metric, roofline of the dominant kernel, CPU-oracle baseline).
+A plain run sets up, spins the clocks up, runs the W warm-up and the K timed steps and prints the line.  ``--full`` adds
+everything else the benchmark measures, each after the timed steps: the same step replayed from a HIP graph
+(``graph_ms_per_step``, timed in a child process), the lazily settled loop, the tile 8 / 16 / 32 sweep BASELINE.json
+names, the per-stage times and the roofline of the dominant kernel, a short training iteration (``extra.train_step``),
+the CPU-oracle baseline, and for N > 1 the per-stage times of every rank.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (one file per array, float32):
+``image.npy`` and ``image_weight.npy`` on a fixed, seeded sample of at most 2^20 pixels (rows of the flattened image),
+and ``grad_<leaf>.npy`` for the five gaussian parameters on a fixed, seeded sample of at most 65 536 gaussians — in
+ascending index order, the same sample for every build given the same arguments.
+
+Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -41,6 +51,8 @@ if str(ROOT) not in sys.path:
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable
 SPIN_UP_SECONDS = float(os.environ.get('MS_BENCH_SPIN_SECONDS', '2.5'))       # single-GPU clock ramp before the warm-up steps (see the timed loop)
+LEAF_NAMES = ('position', 'log_scaling', 'rotation', 'alpha_logit', 'feature')
+DUMP_PIXELS, DUMP_GAUSSIANS, DUMP_SEED = 1 << 20, 1 << 16, 0     # --dump-outputs: sample sizes and their seed
 
 
 def parse_args():
@@ -90,6 +102,11 @@ def parse_args():
                       'across ranks and that every all-to-all split pairs up.  Times mean nothing in this mode')
   p.add_argument('--launcher', action='store_true',
                  help='re-execute under torch.distributed.run even for --gpus 1 (exercises the RCCL path on one GPU)')
+  p.add_argument('--full', action='store_true',
+                 help='after the headline: HIP-graph replay, lazy settle, tile sweep, stage times and roofline, training '
+                      'iteration, CPU baseline (N > 1: per-rank stage times).  The --no-* options drop parts of it')
+  p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                 help='write the last timed step\'s image, image weight and parameter gradients (seeded samples) to DIR/*.npy')
   return p.parse_args()
 
 
@@ -375,6 +392,7 @@ def run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed):
   loss_fn = lambda img, rows: img.sum()
 
   counter = [0]
+  last = {} if args.dump_outputs else None     # --dump-outputs: what the latest step returned
 
   def step_view(v):
     for t in leaves:
@@ -396,9 +414,12 @@ def run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed):
                         backward=not args.forward_only, comm_stats=comm, bounds=bounds)
     elif args.forward_only:
       with torch.no_grad():
-        render_gaussians(g, cam, cfg, use_sh=True)
+        r = render_gaussians(g, cam, cfg, use_sh=True)
     else:
-      render_gaussians(g, cam, cfg, use_sh=True).image.sum().backward()
+      r = render_gaussians(g, cam, cfg, use_sh=True)
+      r.image.sum().backward()
+    if last is not None:
+      last['image'], last['image_weight'] = r.image.detach(), r.image_weight.detach()
 
   def barrier():
     if distributed:
@@ -463,9 +484,12 @@ def run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed):
   comm['entry_waits_per_step'] = (frame_mod.entry_waits - entry0) / max(args.steps, 1)
   barrier()
   elapsed = time.perf_counter() - t0
+  if last is not None:
+    # the gradients the last timed step left on the leaves (every step starts from grad = None)
+    last.update({f'grad_{name}': t.grad for name, t in zip(LEAF_NAMES, leaves) if t.grad is not None})
   if static is not None:
-    # per-stage GPU time of this rank (HIP events at the stage boundaries, a few extra steps after the timed region)
-    # and the overflow flags of the fixed-capacity buffers
+    # the overflow flags of the fixed-capacity buffers; --full: per-stage GPU time of this rank (HIP events at the stage
+    # boundaries, a few extra steps after the timed region)
     from taichi_splatting_amd import sharded
     comm.update(static.comm_bytes)
     for v, st in enumerate(statics):
@@ -473,6 +497,7 @@ def run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed):
       status = st.check()
       if status.get('overlap_overflow') or status.get('bucket_overflow'):
         raise RuntimeError(f"[{mode}] rank {rank}, view {v}: a fixed-capacity buffer overflowed ({status}); the timed frames are invalid")
+  if static is not None and args.full:
     timer = sharded.StageTimer(True)
     for st in statics:
       st.timer = timer
@@ -491,7 +516,7 @@ def run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed):
     dist.all_gather(all_t, t)
     elapsed = max(float(x[0]) for x in all_t)
     per_rank = [float(x[1]) for x in all_t]
-  if distributed and static is not None:
+  if distributed and static is not None and args.full:
     # every rank's stage breakdown on rank 0 (compute / exchange / host can be told apart without rerunning)
     gathered = [None] * world
     dist.all_gather_object(gathered, comm.get('stage_ms'))
@@ -499,7 +524,7 @@ def run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed):
   g.requires_grad_(False)
   for t in leaves:
     t.grad = None
-  return elapsed, per_rank, comm, g
+  return elapsed, per_rank, comm, g, last
 
 
 def main():
@@ -552,6 +577,8 @@ def main():
     modes = ['strips', 'sharded']
   else:
     modes = [args.mode]
+  if args.dump_outputs and (modes != ['single'] or world != 1 or args.train_step):
+    raise SystemExit("bench.py: --dump-outputs writes the outputs of the single-GPU frame step (not of --train-step or N ranks)")
 
   cfg = RasterConfig(tile_size=args.tile, pixel_stride=(1, 1) if args.tile == 8 else (2, 2))
   log(f"building scene n={args.n} size={args.size}")
@@ -577,7 +604,7 @@ def main():
   runs, failed = {}, {}
   for mode in modes:
     try:
-      elapsed, per_rank, comm, g = run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed)
+      elapsed, per_rank, comm, g, last = run_mode(mode, args, cfg, cam, scene, rank, world, device, distributed)
     except Exception as e:          # one decomposition failing must not lose the other's number
       import traceback
       failed[mode] = repr(e)
@@ -585,6 +612,9 @@ def main():
       continue
     ms = elapsed / args.steps * 1e3
     log(f"[{mode}] timed {args.steps} steps: {ms:.3f} ms/step")
+    if last is not None and rank == 0:
+      write_outputs(args.dump_outputs, last)
+      del last
     runs[mode] = {"ms_per_step": round(ms, 3), "value": round(args.n / (ms * 1e-3) / 1e6, 2),
                   "host_syncs_per_step": comm.pop('host_syncs_per_step', None),
                   "strips": "even tile rows" if args.even_strips or world == 1 else "overlap-balanced",
@@ -630,14 +660,14 @@ def main():
                                 "never idles for it); 0 inside a captured HIP graph and with frame.LAZY_SETTLE (opt-in: the look moves "
                                 "to the next frame's entry; `lazy_settle` below times the same loop that way)")
 
-  if rank == 0 and mode == 'single' and not args.forward_only and not args.no_graph:
+  if args.full and rank == 0 and mode == 'single' and not args.forward_only and not args.no_graph:
     # the same step captured in a HIP graph (frame.FrameGraph): no host work between the ~35 launches of a frame.
     # Timed in a child process: a capture that goes wrong takes the process down, and the line above must survive it
     result["graph_ms_per_step"] = graph_step_ms_in_child(args)
     if result["graph_ms_per_step"]:
       result["eager_over_graph"] = round(ms_per_step / result["graph_ms_per_step"], 4)
     log(f"[single] HIP-graph replay: {result['graph_ms_per_step']} ms/step")
-  if rank == 0 and mode == 'single' and not args.forward_only and not args.no_graph:
+  if args.full and rank == 0 and mode == 'single' and not args.forward_only and not args.no_graph:
     # the same eager loop with the overlap total looked at one frame late (frame.LAZY_SETTLE): nothing between a frame's
     # forward and its backward.  Reported beside the default, not instead of it.
     from taichi_splatting_amd import frame as frame_mod
@@ -651,7 +681,7 @@ def main():
     finally:
       frame_mod.settle_all()
       frame_mod.LAZY_SETTLE = False
-  if rank == 0 and mode == 'single' and not args.forward_only and not args.no_sweep:
+  if args.full and rank == 0 and mode == 'single' and not args.forward_only and not args.no_sweep:
     # BASELINE.json configs[3] names the tile-size sweep: the other two sizes, same scene, fewer frames
     sweep = {str(args.tile): ms_per_step}
     for ts in (8, 16, 32):
@@ -660,7 +690,7 @@ def main():
     result["tile_sweep_ms"] = dict(sorted(sweep.items(), key=lambda kv: int(kv[0])))
     log(f"tile sweep {result['tile_sweep_ms']}")
 
-  if rank == 0 and not args.no_stages and mode == 'single':
+  if args.full and rank == 0 and not args.no_stages and mode == 'single':
     g.requires_grad_(False)
     stages, V, K = stage_breakdown(g, cam, cfg, use_sh)
     log(f"stages {stages} V={V} K={K}")
@@ -714,13 +744,13 @@ def main():
                        "hbm_frac_of_peak": round(frame_own / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                        "stage_ms": {k: round(v, 4) for k, v in stages.items()}}
 
-  if rank == 0 and mode == 'single' and world == 1 and not args.forward_only and not args.no_train_step:
+  if args.full and rank == 0 and mode == 'single' and world == 1 and not args.forward_only and not args.no_train_step:
     try:
       result.setdefault("extra", {})["train_step"] = train_iteration(args, g, cam, steps=10, warmup=4)
       log(f"train step {result['extra']['train_step']}")
     except Exception as e:          # a secondary measurement must not lose the headline
       result.setdefault("extra", {})["train_step"] = {"failed": repr(e)}
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
     result["cpu_baseline"] = cpu_baseline(args)
   if distributed and args.dry_run:
     result["dry_run"] = check_collective_logs(rank, world)
@@ -732,6 +762,32 @@ def main():
     import torch.distributed as dist
     dist.barrier()
     dist.destroy_process_group()
+
+
+def write_outputs(out_dir, arrays):
+  """--dump-outputs: the last timed step's outputs as DIR/<name>.npy, float32 (float64 stays float64).  Pixels (rows of
+  the flattened image) and gaussians are sampled with fixed seeds, in ascending order, at most 48 MB in all."""
+  import numpy as np
+  out = Path(out_dir)
+  out.mkdir(parents=True, exist_ok=True)
+  pixels = {k: v.reshape(-1, *v.shape[2:]) for k, v in arrays.items() if k.startswith('image')}
+  gaussians = {k: v for k, v in arrays.items() if k.startswith('grad_')}
+  written = 0
+  for seed, group, k_max in ((DUMP_SEED, pixels, DUMP_PIXELS), (DUMP_SEED + 1, gaussians, DUMP_GAUSSIANS)):
+    if not group:
+      continue
+    total = next(iter(group.values())).shape[0]
+    row_bytes = sum(v[0].numel() * (8 if v.dtype == torch.float64 else 4) for v in group.values())
+    k = min(k_max, (24 << 20) // row_bytes)
+    index = None
+    if total > k:     # k distinct rows in ascending order, the same for every build given the same arguments
+      index = torch.randperm(total, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    for name, v in group.items():
+      v = v if index is None else v.index_select(0, index.to(v.device))
+      v = v.detach().to('cpu', torch.float64 if v.dtype == torch.float64 else torch.float32).contiguous()
+      np.save(out / f'{name}.npy', v.numpy())
+      written += v.numel() * v.element_size()
+  log(f"outputs of the last timed step: {sorted(arrays)} -> {out} ({written / 2**20:.1f} MB)")
 
 
 COUNTER_FILE = ROOT / 'profiles' / 'raster_bwd_counters.json'

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 ROOT = Path(__file__).resolve().parent.parent
-SMALL = ['--n', '200000', '--size', '512', '--steps', '3', '--warmup', '1', '--no-cpu-baseline']
+SMALL = ['--n', '200000', '--size', '512', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline']
 
 
 def run_bench(*extra):

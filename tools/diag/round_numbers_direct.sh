@@ -1,4 +1,4 @@
-B="python bench.py --no-cpu-baseline --steps 50 --no-sweep --no-graph"
+B="python bench.py --full --no-cpu-baseline --steps 50 --no-sweep --no-graph"
 pick() { grep -E "timed|stages" | sed 's/\[bench [0-9:]*\] //'; }
 echo "== config D deterministic"; MS_DETERMINISTIC=1 $B 2>&1 | pick
 echo "== config D forward only"; $B --forward-only --no-stages 2>&1 | pick
