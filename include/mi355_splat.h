@@ -513,9 +513,11 @@ int ms_fractional_update(int kind, int group_type, float* param, const float* gr
 /* All parameter groups of one optimiser step in ONE launch (round 6; the reference loops over its groups on the host,
  * optim/fractional.py:176-195, optim/visibility_aware.py:86-104).  Each group is what ms_fractional_update takes;
  * indexes / weight / total_weight / grad_scale are shared by the groups, as they are in the reference's step().
- * Rows whose length is a multiple of 4 floats (16-byte aligned arrays) move as 16-byte pieces.  A row with
- * weight[i] < 0 is skipped; indexes == NULL means rows 0 .. m_count - 1 (both: the dense mode of
- * ms_optim_visibility_weights).  `groups` is a HOST array. */
+ * Rows whose length is a multiple of 4 floats (16-byte aligned arrays) move as 16-byte pieces.  indexes == NULL
+ * means rows 0 .. m_count - 1, and then a row with weight[i] < 0 (or NaN) is skipped: the dense mode of
+ * ms_optim_visibility_weights.  With an index list every listed row is updated, a negative weight included
+ * (beta^w > 1, as the reference's beta ** w).  Every group is checked before the first launch: an error return
+ * leaves every array as it was.  `groups` is a HOST array. */
 typedef struct ms_optim_group {
   uint32_t struct_size;            /* sizeof(ms_optim_group) */
   int32_t group_type;              /* 0 scalar, 1 vector, 2 local_vector */
@@ -540,8 +542,8 @@ int ms_optim_step_groups(int kind, const ms_optim_group* groups, int num_groups,
  * :86-104): for the m_count rows listed in indexes, running_vis <- ((1 - beta) v^4 + beta running_vis^4)^(1/4),
  * out_weight = v / max(running_vis, floor_eps), total_weight += out_weight, out_grad_scale = 1 / (v + vis_smooth)
  * (out_grad_scale may be NULL).  indexes == NULL (dense mode): row i is point i, and a point with
- * visibility <= skip_threshold is left untouched and gets out_weight = -1 (which ms_optim_step_groups /
- * ms_fractional_update skip) — the reference's `visible = (visibility > 1e-8).nonzero()` without the host
+ * visibility <= skip_threshold is left untouched and gets out_weight = -1 (which ms_optim_step_groups skips in
+ * its dense mode) — the reference's `visible = (visibility > 1e-8).nonzero()` without the host
  * synchronisation (examples/fit_image_gaussians.py:118-119). */
 int ms_optim_visibility_weights(const int64_t* indexes, const float* visibility, int64_t m_count, float vis_beta,
                                 float vis_smooth, float floor_eps, float skip_threshold, float* running_vis,

@@ -94,8 +94,9 @@ fractional_step_kernel(float* __restrict__ lr_step, const int64_t* __restrict__ 
 //   moment update of ms_fractional_step            (vector types: one second moment per point)
 //   step = clamp(step, +-lr * clip); local_vector: step = basis[i] step; *= mask_lr[j]; *= point_lr[idx]
 //   non-finite -> 0;  param[idx] -= step * (1 - exp(-2 weight[i]))
-// A row with weight[i] < 0 is SKIPPED (nothing read or written): ms_optim_visibility_weights marks invisible rows
-// that way in its dense mode.
+// Dense mode (indexes == NULL) only: a row with weight[i] < 0 or NaN is SKIPPED (nothing read or written):
+// ms_optim_visibility_weights marks invisible rows that way.  On an index list every listed row is updated, a negative
+// weight included (beta^w > 1 and a negative saturation, as the reference's beta ** w).
 // The first version (torch.linalg.inv + two batched einsum = rocBLAS batched 3x3 GEMMs, gathers, index_put and a
 // thread-per-point kernel with D-strided accesses) took 166 ms per step for 6 M gaussians (59 floats each).
 // ------------------------------------------------------------------------------------------------
@@ -164,17 +165,18 @@ __device__ __forceinline__ float pow_beta(float e, float log2_beta) { return e =
 // so the shuffles stay uniform.
 // the per-point words every group of a step shares
 struct PointWords {
-  int64_t idx;      // row of the parameter arrays
-  float w;          // step weight (< 0: skip)
+  int64_t idx;      // row of the parameter arrays (< 0: skip the point)
+  float w;          // step weight
   float tw;         // total weight (after this step's weight was added)
   float gscale;     // gradient scale
 };
 
 __device__ __forceinline__ PointWords load_point_words(const CommonArgs& c, int64_t i, bool in_range) {
   PointWords p;
-  p.w = in_range ? c.weight[i] : -1.0f;
-  const bool live = p.w >= 0.0f;                  // (NaN weights skip as well)
-  p.idx = live ? (c.indexes ? c.indexes[i] : i) : 0;
+  p.w = in_range ? c.weight[i] : 0.0f;
+  // the skip sentinel (weight < 0, NaN as well) is the dense mode's alone; a listed row is always updated
+  const bool live = in_range && (c.indexes || p.w >= 0.0f);
+  p.idx = live ? (c.indexes ? c.indexes[i] : i) : -1;
   p.tw = live ? c.total_weight[p.idx] : 1.f;
   p.gscale = (live && c.grad_scale) ? c.grad_scale[i] : 1.f;
   return p;
@@ -185,8 +187,8 @@ __device__ __forceinline__ void update_point(const GroupArgs& a, const PointWord
   static_assert(TYPE != 2 || (VEC == 1 && LPP == 4 && KMAX == 1), "local_vector rows are 2 or 3 floats");
   constexpr int E = KMAX * VEC;
   const float w = pw.w;
-  const bool live = w >= 0.0f;
-  const int64_t idx = pw.idx;
+  const bool live = pw.idx >= 0;
+  const int64_t idx = live ? pw.idx : 0;
   const int d = a.d;
   const float tw = pw.tw;
   const float gscale = pw.gscale;
@@ -518,6 +520,17 @@ extern "C" int ms_optim_step_groups(int kind, const ms_optim_group* groups, int 
   MS_CHECK_ARG(m_count >= 0, "m_count >= 0 expected");
   if (m_count == 0 || num_groups == 0) return 0;
   MS_CHECK_ARG(weight && total_weight, "null pointer");
+  // every group is checked before the first launch: an error return leaves every array as it was
+  for (int gi = 0; gi < num_groups; ++gi) {
+    const ms_optim_group& g = groups[gi];
+    if (g.struct_size != sizeof(ms_optim_group)) {
+      set_error("ms_optim_step_groups: ms_optim_group of another ABI (struct_size %u, this library: %u)", g.struct_size,
+                (unsigned)sizeof(ms_optim_group));
+      return MS_ERR_ABI;
+    }
+    const int rc = check_group(g.group_type, g.d, g.param, g.grad, g.m, g.v, g.basis, "ms_optim_step_groups");
+    if (rc) return rc;
+  }
   hipStream_t s = (hipStream_t)stream;
   const CommonArgs c{indexes, weight, total_weight, grad_scale, m_count};
   FusedArgs f{};
@@ -533,13 +546,6 @@ extern "C" int ms_optim_step_groups(int kind, const ms_optim_group* groups, int 
   };
   for (int gi = 0; gi < num_groups; ++gi) {
     const ms_optim_group& g = groups[gi];
-    if (g.struct_size != sizeof(ms_optim_group)) {
-      set_error("ms_optim_step_groups: ms_optim_group of another ABI (struct_size %u, this library: %u)", g.struct_size,
-                (unsigned)sizeof(ms_optim_group));
-      return MS_ERR_ABI;
-    }
-    const int rc = check_group(g.group_type, g.d, g.param, g.grad, g.m, g.v, g.basis, "ms_optim_step_groups");
-    if (rc) return rc;
     const GroupArgs a{g.param, g.grad, g.m, g.v, g.basis, g.mask_lr, g.point_lr, g.d, g.lr, g.eps, g.clip, g.bias_correction,
                       (float)log2((double)g.beta1), (float)log2((double)g.beta2), nullptr};
     const int shape = pick_shape(g.group_type, a);
