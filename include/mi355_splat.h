@@ -624,6 +624,59 @@ int ms_strip_return_grads(const float* back_rows, const int64_t* send_index, con
 int ms_strip_return_rows(const float* back_rows, const int64_t* send_index, const int32_t* route,
                          int f, int64_t s, float* grad_rows, void* stream);
 
+/* ---- Densification: prune and split the rows of every per-point array of a training state (csrc/densify.hip) --------
+ * Replaces the torch chain of the reference's training loop — params[mask] / torch.cat per tensor and per optimiser
+ * state tensor (optim/parameter_class.py:215-248, examples/fit_image_gaussians.py:190-231) and the child geometry of
+ * misc/renderer2d.py:60-131 — by a fixed launch sequence with one host read (the new row count).
+ *
+ * Destination layout: [kept rows in storage order | children grouped by parent in storage order, `children` per
+ * parent], i.e. torch.cat([x[~(prune | split)], children]).  A row flagged in both masks is pruned.
+ *
+ * ms_densify_plan: prune / split are n bytes each (non-zero = set).  scan (2 n + 1 int32) receives the exclusive scan
+ * of [keep flags | split flags] (scan[i] = destination of kept row i, scan[n] = n_kept, scan[n + i] - n_kept = rank of
+ * split parent i).  counts (device, 4 int32) = (n_kept, n_split_parents, n_out, n); counts_host (pinned, device-visible
+ * host memory, may be NULL) receives the same, valid after the stream is synchronised.  (tmp, tmp_bytes) as for
+ * ms_exclusive_scan_i32.  n * children and 2 n + 1 must fit int32.
+ * ms_densify_table: the source table over the n_out destination rows: src_row (source row) and child_slot
+ * (0 .. children - 1 for a child, -1 for a kept row). */
+int ms_densify_plan(const uint8_t* prune, const uint8_t* split, int64_t n, int children, int32_t* scan,
+                    int32_t* counts, int32_t* counts_host, void* tmp, size_t* tmp_bytes, void* stream);
+int ms_densify_table(const int32_t* scan, int64_t n, int children, int64_t n_out, int32_t* src_row,
+                     int32_t* child_slot, void* stream);
+
+/* ms_densify_move: every array of the step in ONE launch.  Destination row r of each array is source row src_row[r];
+ * child rows (child_slot[r] >= 0) are zero with child_fill 0 (what append_tensors gives optimiser state,
+ * optim/parameter_class.py:236-248) or copy their parent with child_fill 1.  Rows move as 16-byte pieces when
+ * row_bytes % 16 == 0 and both bases are 16-byte aligned, as 4-byte pieces otherwise; row_bytes must be a positive
+ * multiple of 4 (at most 1 MiB).  A source row outside [0, n_src) is written as zeros.  Every descriptor is checked
+ * before the first launch: an error return leaves every array as it was.  `arrays` is a HOST array; src and dst must
+ * not overlap. */
+typedef struct ms_densify_array {
+  uint32_t struct_size;            /* sizeof(ms_densify_array) */
+  int32_t child_fill;              /* 0: child rows are zero, 1: child rows copy the parent */
+  const void* src;                 /* (n_src, row_bytes) */
+  void* dst;                       /* (n_out, row_bytes) */
+  int64_t row_bytes;
+} ms_densify_array;
+int ms_densify_move(const ms_densify_array* arrays, int num_arrays, const int32_t* src_row, const int32_t* child_slot,
+                    int64_t n_src, int64_t n_out, void* stream);
+
+/* Child geometry, in place on rows first .. first + count - 1 of the destination arrays, which hold copies of the
+ * parents (ms_densify_move with child_fill 1); row first + c is child c % children of parent c / children.
+ * z (count, 2 | 3): unit-space samples; scale (count / children, 2 | 3): per-parent factor of the children's
+ * scaling, NULL = 1; depth_offset (count), NULL = 0.  float32.
+ * 2-D (misc/renderer2d.py:36-43,56-67,101-103): position += [v1 s1 | v2 s2] z with v1 = rotation / |rotation|,
+ * v2 = (-v1.y, v1.x), s = max(exp(log_scaling), 1e-4);  log_scaling += log(scale);
+ * depths = max(depths + depth_offset, 1e-6) (depths may be NULL).
+ * 3-D: position += R(q / |q|) (exp(log_scaling) * z), xyzw quaternion as in the projection
+ * (taichi_lib/generic.py:408-416);  log_scaling += log(scale).
+ * A zero offset / a factor of exactly 1 leaves the value as it is, bit for bit. */
+int ms_densify_split2d(float* position, float* log_scaling, const float* rotation, float* depths, int64_t first,
+                       int64_t count, int children, const float* z, const float* scale, const float* depth_offset,
+                       void* stream);
+int ms_densify_split3d(float* position, float* log_scaling, const float* rotation, int64_t first, int64_t count,
+                       int children, const float* z, const float* scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

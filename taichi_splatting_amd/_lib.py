@@ -118,6 +118,14 @@ class OptimGroupC(ctypes.Structure):
   ]
 
 
+class DensifyArrayC(ctypes.Structure):
+  """``ms_densify_array``"""
+  _fields_ = [
+    ('struct_size', ctypes.c_uint32), ('child_fill', c_int32),
+    ('src', c_void_p), ('dst', c_void_p), ('row_bytes', c_int64),
+  ]
+
+
 # name -> (restype, argtypes); must list every function declared in include/mi355_splat.h
 SIGNATURES = {
   'ms_version': (c_int, []),
@@ -170,6 +178,11 @@ SIGNATURES = {
   'ms_optim_step_groups': (c_int, [c_int, POINTER(OptimGroupC), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
   'ms_optim_visibility_weights': (c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float] + [c_void_p] * 5),
   'ms_raster_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, POINTER(RasterConfigC)] + [c_void_p] * 3 + [c_int, c_int, c_int, c_void_p]),
+  'ms_densify_plan': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
+  'ms_densify_table': (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+  'ms_densify_move': (c_int, [POINTER(DensifyArrayC), c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+  'ms_densify_split2d': (c_int, [c_void_p] * 4 + [c_int64, c_int64, c_int] + [c_void_p] * 4),
+  'ms_densify_split3d': (c_int, [c_void_p] * 3 + [c_int64, c_int64, c_int] + [c_void_p] * 3),
 }
 
 

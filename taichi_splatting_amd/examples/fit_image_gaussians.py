@@ -20,8 +20,9 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from ..data_types import Gaussians2D, RasterConfig
+from ..misc.densify import densify_uniform_split_gaussians2d
 from ..misc.renderer2d import point_basis, project_gaussians2d, uniform_split_gaussians2d
-from ..optim import ParameterClass, VisibilityAwareLaProp
+from ..optim import ParameterClass, VisibilityAwareLaProp, plan_densify
 from ..rasterizer import rasterize
 from ..testing import random_2d_gaussians
 
@@ -100,14 +101,21 @@ def take_n(score: torch.Tensor, n: int, descending: bool) -> torch.Tensor:
 
 
 def split_prune(params: ParameterClass, t: float, target: int, prune_rate: float,
-                heuristics: Tuple[torch.Tensor, torch.Tensor]) -> Tuple[ParameterClass, Dict[str, int]]:
-  """Prune the cheapest points, split the highest-scoring ones towards ``target`` points."""
+                heuristics: Tuple[torch.Tensor, torch.Tensor], fused: bool = False) -> Tuple[ParameterClass, Dict[str, int]]:
+  """Prune the cheapest points, split the highest-scoring ones towards ``target`` points.  ``fused``: the rows move and
+  the children are made by the densification kernels (``misc/densify.py``) instead of the torch chain; same masks, same
+  random draws."""
   prune_cost, split_score = heuristics
   n = params.batch_size[0]
   prune_mask = take_n(prune_cost, int(prune_rate * n * (1 - t)), descending=False)
   split_mask = take_n(split_score, max(0, (target - n) + int(prune_mask.sum())), descending=True)
   both = split_mask & prune_mask
   split_mask, prune_mask = split_mask ^ both, prune_mask ^ both
+
+  if fused:
+    plan = plan_densify(prune_mask, split_mask, 2)
+    kept = densify_uniform_split_gaussians2d(params, prune_mask, split_mask, n=2, random_axis=True, plan=plan)
+    return kept, dict(split=plan.n_split, prune=plan.n - plan.n_kept - plan.n_split)
 
   to_split = params[split_mask] if bool(split_mask.any()) else None
   kept = params[~(split_mask | prune_mask)]
@@ -120,8 +128,9 @@ def split_prune(params: ParameterClass, t: float, target: int, prune_rate: float
 def fit(ref_image: torch.Tensor, n: int = 1000, iters: int = 500, target: Optional[int] = None, seed: int = 0,
         tile_size: int = 16, antialias: bool = False, max_lr: float = 0.5, min_lr: float = 0.1, epoch: int = 8,
         max_epoch: int = 32, prune_rate: float = 0.025, opacity_reg: float = 1e-5, scale_reg: float = 0.1,
-        verbose: bool = False):
-  """Returns (final image, params, history of (iteration, psnr, n))."""
+        verbose: bool = False, fused_densify: bool = False):
+  """Returns (final image, params, history of (iteration, psnr, n)).  ``fused_densify``: split / prune with the
+  densification kernels."""
   device = ref_image.device
   h, w = ref_image.shape[:2]
   torch.manual_seed(seed)
@@ -143,7 +152,7 @@ def fit(ref_image: torch.Tensor, n: int = 1000, iters: int = 500, target: Option
     if target and iteration + epoch_size < iters:
       t_points = min(math.sqrt(t * 2), 1.0)
       goal = math.ceil(params.batch_size[0] * (1 - t_points) + t_points * target)
-      params, counts = split_prune(params, t, goal, prune_rate, heuristics)
+      params, counts = split_prune(params, t, goal, prune_rate, heuristics, fused=fused_densify)
       metrics.update(counts)
     iteration += epoch_size
     history.append((iteration, metrics['psnr'], metrics['n']))
@@ -167,6 +176,7 @@ def main():
   p.add_argument('--tile_size', type=int, default=16)
   p.add_argument('--antialias', action='store_true')
   p.add_argument('--write', type=str, default=None)
+  p.add_argument('--fused-densify', action='store_true', help='split / prune with the fused densification kernels')
   args = p.parse_args()
   device = torch.device('cuda:0')
   if args.image_file is None:
@@ -180,7 +190,8 @@ def main():
     ref = (ref.float() / 255 if ref.dtype == torch.uint8 else ref.float()).to(device).contiguous()
   print(f"image {ref.shape[1]}x{ref.shape[0]}")
   image, params, history = fit(ref, n=args.n, iters=args.iters, target=args.target or (args.n if args.prune else None),
-                               seed=args.seed, tile_size=args.tile_size, antialias=args.antialias, verbose=True)
+                               seed=args.seed, tile_size=args.tile_size, antialias=args.antialias, verbose=True,
+                               fused_densify=args.fused_densify)
   print(f"final PSNR {history[-1][1]:.2f} dB with {params.batch_size[0]} gaussians")
   if args.write:
     torch.save(image.cpu(), args.write)

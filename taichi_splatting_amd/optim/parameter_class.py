@@ -193,3 +193,9 @@ class ParameterClass:
 
   def append(self, params: 'ParameterClass'):
     return self.append_tensors(_map(params.tensors, lambda t: t.detach()))
+
+  def densify(self, prune_mask: torch.Tensor, split_mask: torch.Tensor, children: int = 2, **kwargs):
+    """``self[~(prune_mask | split_mask)].append_tensors(children of the split rows)`` in one fused step on the GPU
+    (``optim/densify.py``: one host read, one move launch for all tensors and state tensors)."""
+    from .densify import densify
+    return densify(self, prune_mask, split_mask, children, **kwargs)
