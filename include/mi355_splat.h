@@ -677,6 +677,38 @@ int ms_densify_split2d(float* position, float* log_scaling, const float* rotatio
 int ms_densify_split3d(float* position, float* log_scaling, const float* rotation, int64_t first, int64_t count,
                        int children, const float* z, const float* scale, void* stream);
 
+/* ---- Photometric loss: (1 - lambda) L1 + lambda (1 - SSIM), forward and backward (csrc/loss.hip) ---------------------
+ * An addition, not a replacement: the reference has no loss (its demo calls torch's mse_loss).  image and target are
+ * contiguous (H, W, C) arrays of `dtype`, the layout the rasterizer writes and its backward reads; 1 <= C <= 4.
+ *
+ * Per channel, with G the separable 11-tap window exp(-k^2 / (2 1.5^2)) normalised to sum 1, C1 = 0.01^2, C2 = 0.03^2:
+ *   mu1 = G*x   mu2 = G*y   s11 = G*x^2 - mu1^2   s22 = G*y^2 - mu2^2   s12 = G*xy - mu1 mu2
+ *   ssim = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2))
+ *   loss = (1 - lambda) mean|x - y| + lambda (1 - mean ssim)
+ * padding MS_PAD_SAME zero-pads like conv2d(padding = 5): the ssim map is (H, W, C).  MS_PAD_VALID keeps the elements
+ * whose window lies inside the image: the map is (H - 10, W - 10, C) and H, W >= 11 is required.  mean|x - y| is over
+ * the H W C image elements, mean ssim over the map elements.
+ *
+ * ms_photometric_fwd: out_loss (device, 3 values of `dtype`) = {loss, mean|x - y|, mean ssim}.  map_a, map_b, map_c:
+ * all three NULL, or three arrays of the ssim map's shape that receive, per element, what the backward needs:
+ * A = d ssim/d mu1 - 2 mu1 B - mu2 C,  B = d ssim/d s11,  C = d ssim/d s12.  tmp holds one pair of partial sums
+ * (double) per workgroup, added in a fixed order by a second kernel: the result is bit-reproducible (no atomics).
+ * tmp == NULL: *tmp_bytes receives the size tmp must have and nothing is launched.
+ * ms_photometric_bwd: grad_image (H, W, C) =
+ *   grad_out * [ (1 - lambda) / (H W C) sign(x - y) - lambda / (map elements) (G*A + 2 x G*B + y G*C) ],
+ * sign(0) = 0; the maps are those of a forward with the same sizes and padding (`valid`: absent map elements count as
+ * zero, the full correlation).  grad_out is ONE value of `dtype` in DEVICE memory: neither call reads back to the host.
+ * There is no gradient for target.
+ * MS_ERR_BAD_ARG: null pointer, H, W <= 0, C outside 1..4, unknown padding, `valid` with a side under 11, lambda
+ * outside [0, 1]; MS_ERR_UNSUPPORTED: unknown dtype; MS_ERR_TMP_TOO_SMALL. */
+enum { MS_PAD_SAME = 0, MS_PAD_VALID = 1 };
+int ms_photometric_fwd(const void* image, const void* target, int H, int W, int C, int dtype, int padding,
+                       double lambda, void* map_a, void* map_b, void* map_c, void* tmp, size_t* tmp_bytes,
+                       void* out_loss, void* stream);
+int ms_photometric_bwd(const void* image, const void* target, const void* map_a, const void* map_b, const void* map_c,
+                       const void* grad_out, int H, int W, int C, int dtype, int padding, double lambda,
+                       void* grad_image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from . import cuda_lib as hip_lib
 from . import optim
 from .perspective import CameraParams
 from .taichi_queue import TaichiQueue, taichi_queue, queued
+from .loss import l1_ssim_loss, ssim
 
 __version__ = '0.5.0'       # = MS_VERSION 500 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -27,6 +28,7 @@ __all__ = [
   'RasterConfig', 'evaluate_sh_at',
   'rasterize', 'rasterize_with_tiles',
   'perspective', 'TaichiQueue',
+  'l1_ssim_loss', 'ssim',
 ]
 
 

@@ -24,6 +24,7 @@ BACKWARD_ALL, BACKWARD_GAUSSIANS, BACKWARD_RASTER = 0, 1, 2   # ms_frame_grads.s
 BOUNDARY_AXIS_SIGMA, BOUNDARY_COVARIANCE = 0, 1
 MAPPER_DIRECT, MAPPER_PRESORT = 0, 1               # ms_frame_grads.boundary_form
 ABI_VERSION = 500  # MS_VERSION of include/mi355_splat.h this binding was written against (tests/test_abi.py)
+PAD_SAME, PAD_VALID = 0, 1                         # MS_PAD_SAME / MS_PAD_VALID (ms_photometric_*)
 MOMENT_ROW = 16   # MS_MOMENT_ROW of include/mi355_splat.h
 SPLAT_ROW = 16    # MS_SPLAT_ROW
 
@@ -183,6 +184,8 @@ SIGNATURES = {
   'ms_densify_move': (c_int, [POINTER(DensifyArrayC), c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
   'ms_densify_split2d': (c_int, [c_void_p] * 4 + [c_int64, c_int64, c_int] + [c_void_p] * 4),
   'ms_densify_split3d': (c_int, [c_void_p] * 3 + [c_int64, c_int64, c_int] + [c_void_p] * 3),
+  'ms_photometric_fwd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p, c_void_p]),
+  'ms_photometric_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
 }
 
 

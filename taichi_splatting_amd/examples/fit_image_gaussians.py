@@ -20,6 +20,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from ..data_types import Gaussians2D, RasterConfig
+from ..loss import l1_ssim_loss
 from ..misc.densify import densify_uniform_split_gaussians2d
 from ..misc.renderer2d import point_basis, project_gaussians2d, uniform_split_gaussians2d
 from ..optim import ParameterClass, VisibilityAwareLaProp, plan_densify
@@ -55,8 +56,10 @@ def as_gaussians(params: ParameterClass) -> Gaussians2D:
 
 
 def train_epoch(params: ParameterClass, ref_image: torch.Tensor, config: RasterConfig, epoch_size: int,
-                opacity_reg: float = 0.0, scale_reg: float = 0.0):
-  """``epoch_size`` optimiser steps; returns (last image, accumulated (prune_cost, split_score), params)."""
+                opacity_reg: float = 0.0, scale_reg: float = 0.0, loss: str = 'mse'):
+  """``epoch_size`` optimiser steps; returns (last image, accumulated (prune_cost, split_score), params).
+  ``loss``: 'mse', or 'l1_ssim' for the fused 0.8 L1 + 0.2 (1 - SSIM) in place of the mse term."""
+  image_loss = dict(mse=torch.nn.functional.mse_loss, l1_ssim=l1_ssim_loss)[loss]
   h, w = ref_image.shape[:2]
   n = params.batch_size[0]
   heuristic = torch.zeros((n, 2), device=ref_image.device)
@@ -69,9 +72,9 @@ def train_epoch(params: ParameterClass, ref_image: torch.Tensor, config: RasterC
                          features=gaussians.feature, image_size=(w, h), config=config)
       image = raster.image
       scale = torch.exp(gaussians.log_scaling) / min(w, h)
-      loss = (torch.nn.functional.mse_loss(image, ref_image) + opacity_reg * gaussians.opacity.mean()
-              + scale_reg * scale.pow(2).mean())
-      loss.backward()
+      total = (image_loss(image, ref_image) + opacity_reg * gaussians.opacity.mean()
+               + scale_reg * scale.pow(2).mean())
+      total.backward()
     visibility = raster.visibility
     visible = (visibility > 1e-8).nonzero().squeeze(1)
     params.step(indexes=visible, visibility=visibility[visible], basis=point_basis(gaussians[visible]).detach())
@@ -128,9 +131,11 @@ def split_prune(params: ParameterClass, t: float, target: int, prune_rate: float
 def fit(ref_image: torch.Tensor, n: int = 1000, iters: int = 500, target: Optional[int] = None, seed: int = 0,
         tile_size: int = 16, antialias: bool = False, max_lr: float = 0.5, min_lr: float = 0.1, epoch: int = 8,
         max_epoch: int = 32, prune_rate: float = 0.025, opacity_reg: float = 1e-5, scale_reg: float = 0.1,
-        verbose: bool = False, fused_densify: bool = False):
+        verbose: bool = False, fused_densify: bool = False, loss: str = 'mse'):
   """Returns (final image, params, history of (iteration, psnr, n)).  ``fused_densify``: split / prune with the
-  densification kernels."""
+  densification kernels.  ``loss``: 'mse' or 'l1_ssim' (the fused photometric loss replaces the mse term)."""
+  if loss not in ('mse', 'l1_ssim'):
+    raise ValueError(f"loss must be 'mse' or 'l1_ssim' (got {loss!r})")
   device = ref_image.device
   h, w = ref_image.shape[:2]
   torch.manual_seed(seed)
@@ -147,7 +152,7 @@ def fit(ref_image: torch.Tensor, n: int = 1000, iters: int = 500, target: Option
     t = (iteration + epoch_size * 0.5) / iters
     params.set_learning_rate(position=log_lerp(t, max_lr, min_lr))
     start = time.time()
-    image, heuristics = train_epoch(params, ref_image, config, epoch_size, opacity_reg, scale_reg)
+    image, heuristics = train_epoch(params, ref_image, config, epoch_size, opacity_reg, scale_reg, loss)
     metrics = dict(psnr=psnr(ref_image, image), n=params.batch_size[0])
     if target and iteration + epoch_size < iters:
       t_points = min(math.sqrt(t * 2), 1.0)
@@ -177,6 +182,7 @@ def main():
   p.add_argument('--antialias', action='store_true')
   p.add_argument('--write', type=str, default=None)
   p.add_argument('--fused-densify', action='store_true', help='split / prune with the fused densification kernels')
+  p.add_argument('--loss', choices=('mse', 'l1_ssim'), default='mse', help='image term of the objective')
   args = p.parse_args()
   device = torch.device('cuda:0')
   if args.image_file is None:
@@ -191,7 +197,7 @@ def main():
   print(f"image {ref.shape[1]}x{ref.shape[0]}")
   image, params, history = fit(ref, n=args.n, iters=args.iters, target=args.target or (args.n if args.prune else None),
                                seed=args.seed, tile_size=args.tile_size, antialias=args.antialias, verbose=True,
-                               fused_densify=args.fused_densify)
+                               fused_densify=args.fused_densify, loss=args.loss)
   print(f"final PSNR {history[-1][1]:.2f} dB with {params.batch_size[0]} gaussians")
   if args.write:
     torch.save(image.cpu(), args.write)
