@@ -55,48 +55,53 @@ extern "C" void hm_project_fwd_f32(const double* pos, const double* ls, const do
   }
 }
 
-extern "C" void hm_project_bwd(const double* pos, const double* ls, const double* rot, const double* al,
-                               const double* T, const double* P, int W, int H, double blur, double margin,
-                               int64_t n, const double* g_points7, const double* g_depth, double* d_pos,
-                               double* d_ls, double* d_rot, double* d_al, double* d_cam16) {
-  Camera<double> cam = make_cam(T, P);
-  ProjParams<double> pp{(double)W, (double)H, 1.0, 2.0, blur, margin, 1.0 / 255.0};
-  for (int k = 0; k < 16; ++k) d_cam16[k] = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    ProjState<double> st;
-    project_forward(pos + i * 3, ls + i * 3, rot + i * 4, al[i], cam, pp, st);
-    project_backward(pos + i * 3, cam, st, g_points7 + i * 7, g_depth[i], d_pos + i * 3, d_ls + i * 3,
-                     d_rot + i * 4, d_al[i], d_cam16);
-  }
-}
-
-// float32 instantiation of the projection backward (inputs / outputs travel as double, the arithmetic is float):
-// the conditioning of the hand-derived chain in the PRODUCT precision can be measured without a GPU
-// (tests/test_hostmath.py::test_projection_backward_f32_conditioning).
-extern "C" void hm_project_bwd_f32(const double* pos, const double* ls, const double* rot, const double* al,
-                                   const double* T, const double* P, int W, int H, double blur, double margin,
-                                   int64_t n, const double* g_points7, const double* g_depth, double* d_pos,
-                                   double* d_ls, double* d_rot, double* d_al, double* d_cam16) {
-  Camera<float> cam;
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) cam.t[i][j] = (float)T[i * 4 + j];
-  cam.fx = (float)P[0]; cam.fy = (float)P[1]; cam.cx = (float)P[2]; cam.cy = (float)P[3];
-  ProjParams<float> pp{(float)W, (float)H, 1.0f, 2.0f, (float)blur, (float)margin, 1.0f / 255.0f};
-  float cam_grad[16];
+// project_backward on n rows in precision T (inputs / outputs travel as double, the arithmetic is T).  g_cov (n, 3),
+// may be NULL: dL/d(a, b, c) of the blurred 2D covariance, added to what g_points7's (axis, sigma) columns give — the
+// way every product frame and every multi-GPU rank step calls project_backward (csrc/gaussian_bwd.hip).
+template <typename T>
+static void project_bwd(const double* pos, const double* ls, const double* rot, const double* al, const double* Tm,
+                        const double* P, int W, int H, double blur, double margin, int64_t n, const double* g_points7,
+                        const double* g_depth, const double* g_cov, double* d_pos, double* d_ls, double* d_rot,
+                        double* d_al, double* d_cam16) {
+  Camera<T> cam;
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) cam.t[i][j] = (T)Tm[i * 4 + j];
+  cam.fx = (T)P[0]; cam.fy = (T)P[1]; cam.cx = (T)P[2]; cam.cy = (T)P[3];
+  ProjParams<T> pp{(T)W, (T)H, T(1), T(2), (T)blur, (T)margin, T(1) / T(255)};
+  T cam_grad[16];
   for (int k = 0; k < 16; ++k) cam_grad[k] = 0;
   for (int64_t i = 0; i < n; ++i) {
-    float p[3], l[3], q[4], gp[7], dp_[3], dl[3], dq[4], da;
-    for (int k = 0; k < 3; ++k) { p[k] = (float)pos[i * 3 + k]; l[k] = (float)ls[i * 3 + k]; }
-    for (int k = 0; k < 4; ++k) q[k] = (float)rot[i * 4 + k];
-    for (int k = 0; k < 7; ++k) gp[k] = (float)g_points7[i * 7 + k];
-    ProjState<float> st;
-    project_forward(p, l, q, (float)al[i], cam, pp, st);
-    project_backward(p, cam, st, gp, (float)g_depth[i], dp_, dl, dq, da, cam_grad);
+    T p[3], l[3], q[4], gp[7], gc[3] = {0, 0, 0}, dp_[3], dl[3], dq[4], da;
+    for (int k = 0; k < 3; ++k) { p[k] = (T)pos[i * 3 + k]; l[k] = (T)ls[i * 3 + k]; }
+    for (int k = 0; k < 4; ++k) q[k] = (T)rot[i * 4 + k];
+    for (int k = 0; k < 7; ++k) gp[k] = (T)g_points7[i * 7 + k];
+    if (g_cov) for (int k = 0; k < 3; ++k) gc[k] = (T)g_cov[i * 3 + k];
+    ProjState<T> st;
+    project_forward(p, l, q, (T)al[i], cam, pp, st);
+    project_backward(p, cam, st, gp, (T)g_depth[i], dp_, dl, dq, da, cam_grad, g_cov ? gc : nullptr);
     for (int k = 0; k < 3; ++k) { d_pos[i * 3 + k] = dp_[k]; d_ls[i * 3 + k] = dl[k]; }
     for (int k = 0; k < 4; ++k) d_rot[i * 4 + k] = dq[k];
     d_al[i] = da;
   }
   for (int k = 0; k < 16; ++k) d_cam16[k] = cam_grad[k];
 }
+
+#define HM_BWD_ARGS const double* pos, const double* ls, const double* rot, const double* al, const double* T, \
+                    const double* P, int W, int H, double blur, double margin, int64_t n, const double* g_points7, \
+                    const double* g_depth
+#define HM_BWD_OUTS double* d_pos, double* d_ls, double* d_rot, double* d_al, double* d_cam16
+#define HM_BWD_PASS(g_cov) pos, ls, rot, al, T, P, W, H, blur, margin, n, g_points7, g_depth, g_cov, d_pos, d_ls, d_rot, d_al, d_cam16
+
+extern "C" void hm_project_bwd(HM_BWD_ARGS, HM_BWD_OUTS) { project_bwd<double>(HM_BWD_PASS(nullptr)); }
+
+// float32 instantiation: the conditioning of the hand-derived chain in the PRODUCT precision can be measured without a
+// GPU (tests/test_hostmath.py::test_projection_backward_f32_conditioning)
+extern "C" void hm_project_bwd_f32(HM_BWD_ARGS, HM_BWD_OUTS) { project_bwd<float>(HM_BWD_PASS(nullptr)); }
+
+// the covariance entry: the protocol of hm_project_bwd plus g_cov (n, 3)
+extern "C" void hm_project_bwd_cov(HM_BWD_ARGS, const double* g_cov, HM_BWD_OUTS) { project_bwd<double>(HM_BWD_PASS(g_cov)); }
+
+// (tests/test_hostmath.py::test_projection_backward_cov_f32_rows measures T_cov with it)
+extern "C" void hm_project_bwd_cov_f32(HM_BWD_ARGS, const double* g_cov, HM_BWD_OUTS) { project_bwd<float>(HM_BWD_PASS(g_cov)); }
 
 template <int DEG>
 static void sh_eval(const double* params, const double* positions, const int64_t* indexes, const double* cam,
