@@ -3,7 +3,7 @@
 
 ``render_gaussians`` (reference ``renderer.py:23-108``) runs through here: projection, SH colour, the tile mapper
 (overlap count / scan / emission in storage order, stable sort on the tile bits, ranges, per-tile depth sort — or, per
-scene shape, the depth pre-sort sequence: ``_choose_mapper``) and the raster forward are enqueued by two C calls, the
+scene shape, the depth pre-sort sequence: ``ShapeRecord``) and the raster forward are enqueued by two C calls, the
 backward pass by one (raster backward + ONE pass over the gaussians).  Differences to the reference's orchestration, none of
 them visible in results:
 
@@ -19,19 +19,18 @@ them visible in results:
 from __future__ import annotations
 
 import collections
-import contextlib
 import ctypes
-import gc
 from dataclasses import dataclass, replace
 import os
-import threading
-import time
 from typing import Optional, Tuple
 import weakref
 
 import torch
 
 from . import _lib
+# (re-exported: callers, tests and tools reach the moved names through this module)
+from ._frame_host import (GRAPH_K_WORDS, K_PENDING, K_SLOTS, MOMENTS_LRU, KSlots, _drop_moments, _k_host, _lock, _moments,
+                          _moments_buffer, _moments_pinned, k_ring, parked_gc, pinned_word, release_moments, wait_for_k)   # noqa: F401
 from .data_types import RasterConfig
 
 # MS_FRAME=legacy: render_gaussians composes the modular operators (project_to_image, evaluate_sh_at, map_to_tiles,
@@ -41,8 +40,7 @@ USE_FRAME = os.environ.get('MS_FRAME', 'frame') != 'legacy'
 K_SLACK = 1.25            # capacity = K_SLACK x the largest overlap total seen for this scene shape
 K_GRANULE = 1 << 16
 
-_k_capacity = {}          # scene-shape key -> overlap-list capacity
-_mapper_mode = {}         # scene-shape key -> _lib.MAPPER_DIRECT / MAPPER_PRESORT (see _choose_mapper)
+_shapes = {}              # scene-shape key -> ShapeRecord: what the executor has learnt about frames of that shape
 # overlaps per gaussian above which the depth pre-sort sequence is the faster mapper, with some hysteresis.  Same box,
 # direct - presort per frame: K/N 2.13 (config D) -0.16 ms, 2.25 (1 M, tile 32) -0.06, 2.59 (3 M) -0.08, 3.34 (1.5 M)
 # -0.04, 3.65 (config D at tile 8) +0.06 (tools/diag/ab_mapper.sh)
@@ -51,17 +49,7 @@ PRESORT_ABOVE, DIRECT_BELOW = 3.6, 3.4
 # kernel writes the length of a run above that size into a pinned word (ms_frame_inputs.longest_run_host); a scene
 # shape that shows one maps with the pre-sort from the next frame on, whatever its overlaps per gaussian.
 LONG_RUN_LIMIT = 16384
-_run_words = {}           # scene-shape key -> (pinned int32[1] tensor, numpy view)
-_presort_sticky = set()   # scene shapes that showed a run above LONG_RUN_LIMIT
-_k_host = {}              # device index -> KSlots: a ring of pinned int32 words, ONE PER FRAME IN FLIGHT
-_moments = collections.OrderedDict()   # (device index, stream, n, deterministic) -> accumulator rows, zero between frames
-_moments_pinned = set()   # keys whose buffer address is baked into a captured HIP graph: never evicted
 _identity = {}            # (device index, n) -> arange(n) int64
-_lock = threading.RLock() # guards the caches above and serialises the enqueue of a backward pass (ctypes drops the GIL)
-
-MOMENTS_LRU = 4           # accumulator buffers kept per device (scene sizes / streams alternating in one process)
-K_SLOTS = 64              # pinned K words per device; a frame holds one from its forward until it has looked at K
-GRAPH_K_WORDS = 1024      # pinned K words per device for frames captured into HIP graphs
 SPLIT_LONG_RUNS = os.environ.get('MS_SPLIT_LONG_RUNS', '1') not in ('', '0')   # A/B switch of the long-run segments
 # run-time parameters of the segments (ms_frame_desc.split_long_runs / split_seg_len): a run is cut when it is longer than
 # SPLIT_MIN_RUN entries (0: the library's default, 16 384) into segments of >= SPLIT_SEG_LEN entries (0: default);
@@ -109,8 +97,7 @@ VISIBILITY_FROM_BACKWARD = os.environ.get('MS_VISIBILITY_FROM_BACKWARD', '0') no
 SH_SIDE_STREAM = os.environ.get('MS_SH_SIDE_STREAM', '1') not in ('', '0')
 _side_streams = {}        # device index -> the executor's second stream
 visibility_passes = 0     # deferred frames whose visibility was read before their backward pass had written it
-LAZY_AFTER = 3
-_stable_frames = {}       # scene-shape key -> settled frames in a row that fitted the remembered capacity
+LAZY_AFTER = 3            # settled frames in a row that fitted the remembered capacity before a shape may settle lazily
 _unsettled = collections.deque()   # FrameStates whose overlap total the host has not looked at yet (oldest first)
 
 host_syncs = 0            # looks at an overlap total BETWEEN a frame's forward and its backward / return to the caller
@@ -139,16 +126,100 @@ def frame_supported(feature: torch.Tensor, config: RasterConfig, use_sh: bool) -
   return 1 <= f <= 4 and feature.is_cuda
 
 
+def _shape_key(device, n, image_size, config, tile_rows, depth16):
+  return (device.index, int(n), int(image_size[0]), int(image_size[1]), config.tile_size,
+          None if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1])), bool(depth16))
+
+
+def round_capacity(k: int) -> int:
+  k = max(int(k), 1)
+  return min((k + K_GRANULE - 1) // K_GRANULE * K_GRANULE, (1 << 31) - 1)
+
+
+class ShapeRecord:
+  """What the executor has learnt about the frames of one scene shape, and the policy of its next frame: which mapper
+  sequence it takes, whether it carries the segment launches, what capacity it gets, whether it may settle lazily.
+  Shared by every thread that renders (a viewer next to a trainer): read and updated under ``_lock``."""
+  __slots__ = ('capacity', 'mapper', 'run_word', 'run_view', 'sticky', 'stable', 'depth16')
+
+  def __init__(self, depth16: bool = False):
+    self.capacity = 0           # overlap-list capacity
+    self.mapper = None          # _lib.MAPPER_DIRECT / MAPPER_PRESORT of the next frame; None: no frame of the shape yet
+    self.run_word = self.run_view = None   # pinned int32[1] tensor + numpy view (ms_frame_inputs.longest_run_host)
+    self.sticky = False         # the shape showed a run above LONG_RUN_LIMIT
+    self.stable = 0             # settled frames in a row that fitted the remembered capacity
+    self.depth16 = depth16
+
+  def plan(self, capturing: bool, split_long_runs: bool, split_always: bool, split_min_run: int, split_seg_len: int):
+    """The next frame of this shape: (capacity, mapper, ms_frame_desc.split_long_runs, split_seg_len, address of the run
+    word or None).  Never pins the run word under capture: pinning host memory inside a capture invalidates it."""
+    # what the per-tile sort of an earlier frame of this shape reported (no synchronisation: the word is a frame or two old)
+    if self.run_word is None and not capturing:
+      self.run_word, self.run_view = pinned_word()
+    if self.run_word is not None and int(self.run_view[0]) > LONG_RUN_LIMIT and not self.sticky:
+      self.sticky = True
+      self.mapper = _lib.MAPPER_PRESORT
+    # the same in every call of this frame.  The FIRST frame of a scene shape (nothing known about how its overlaps are
+    # spread) takes the sequence whose cost does not depend on that — the pre-sort, 0.1-0.2 ms dearer on a scene like
+    # config D — and carries the segment launches: a pile-up then costs its first frame what it costs every frame, not
+    # the 7 ms of ONE workgroup sorting a 244 000-entry run plus one workgroup rasterizing it (round 5's first frame of
+    # that shape: 11.1 ms against 1.67 steady; tools/sweep_scenes.py guards first <= 3 x steady).  The second frame
+    # runs what observe() settled on.
+    first_of_shape = self.mapper is None
+    # a shape that showed a run above LONG_RUN_LIMIT also has its long runs rasterized in segments (the raster forward
+    # reports such runs through the same word on either mapper sequence)
+    # (field value 1 = the default threshold, > 1 = the threshold itself; the library raises thresholds below 256)
+    split_on = split_long_runs and (split_always or first_of_shape or self.sticky)
+    return (self.capacity, _lib.MAPPER_PRESORT if first_of_shape else self.mapper,
+            (max(2, split_min_run) if split_min_run > 0 else 1) if split_on else 0, split_seg_len,
+            None if self.run_word is None else self.run_word.data_ptr())
+
+  def choose_mapper(self, k_total: int, n: int):
+    """Remember which launch sequence the next frame of this scene shape maps its tiles with (same lists either way).
+    16 bit depth keys always take the pre-sort: two passes over n pairs instead of four, 4-byte pairs through the tile
+    sort (1 M gaussians, K / n 2.45: 0.148 ms against 0.185)."""
+    ratio = k_total / max(n, 1)
+    if self.depth16 or self.sticky or ratio > PRESORT_ABOVE:
+      self.mapper = _lib.MAPPER_PRESORT
+    elif ratio < DIRECT_BELOW or self.mapper is None:
+      self.mapper = _lib.MAPPER_DIRECT
+
+  def observe(self, k_total: int, n: int, overflowed: bool):
+    """A settled frame of this shape produced ``k_total`` overlaps from ``n`` gaussians."""
+    self.capacity = max(self.capacity, round_capacity(k_total * K_SLACK))
+    self.choose_mapper(k_total, n)
+    self.stable = 0 if overflowed else self.stable + 1
+
+  def release(self, force: bool = False):
+    self.capacity, self.mapper, self.sticky, self.stable = 0, None, False, 0
+    # the run word stays (4 pinned bytes per scene shape): a frame still in flight, or a captured one at every replay,
+    # writes its word — handing the memory back to the allocator would let that write land in somebody else's tensor
+    if force:
+      self.run_word = self.run_view = None
+    elif self.run_view is not None:
+      self.run_view[0] = 0
+
+
+def shape_record(key, create: bool = False) -> Optional[ShapeRecord]:
+  """The record of a scene shape (``_shape_key``; ``('2d',) + _shape_key`` for ``rasterize``), or None."""
+  with _lock:
+    rec = _shapes.get(key)
+    if rec is None and create:
+      rec = _shapes[key] = ShapeRecord(depth16=bool(key) and key[-1] is True)
+  return rec
+
+
 def set_overlap_capacity(n: int, image_size, config: RasterConfig, capacity: int, device=None, tile_rows=None,
                          use_depth16: bool = False):
   """Fix the overlap-list capacity for a scene shape (needed before capturing a frame in a HIP graph when no eager
   frame of that shape has run yet)."""
   dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-  key = _shape_key(dev, n, image_size, config, tile_rows, use_depth16)
-  _k_capacity[key] = _round_capacity(capacity)
-  _choose_mapper(key, int(capacity / K_SLACK), n)
+  with _lock:
+    rec = shape_record(_shape_key(dev, n, image_size, config, tile_rows, use_depth16), create=True)
+    rec.capacity = round_capacity(capacity)
+    rec.choose_mapper(int(capacity / K_SLACK), n)
   if not torch.cuda.is_current_stream_capturing():
-    _k_ring(dev)               # pinned words must exist before a capture starts
+    k_ring(dev)                # pinned words must exist before a capture starts
 
 
 def set_split_policy(min_run: int = 0, seg_len: int = 0, always: bool = False):
@@ -156,143 +227,6 @@ def set_split_policy(min_run: int = 0, seg_len: int = 0, always: bool = False):
   global SPLIT_MIN_RUN, SPLIT_SEG_LEN, SPLIT_ALWAYS
   assert min_run >= 0 and seg_len >= 0
   SPLIT_MIN_RUN, SPLIT_SEG_LEN, SPLIT_ALWAYS = int(min_run), int(seg_len), bool(always)
-
-
-def _choose_mapper(key, k_total: int, n: int):
-  """Remember which launch sequence the next frame of this scene shape maps its tiles with (same lists either way).
-  16 bit depth keys (the last entry of a shape key) always take the pre-sort: two passes over n pairs instead of four,
-  4-byte pairs through the tile sort (1 M gaussians, K / n 2.45: 0.148 ms against 0.185)."""
-  ratio = k_total / max(n, 1)
-  now = _mapper_mode.get(key, _lib.MAPPER_DIRECT)
-  if (key and key[-1] is True) or key in _presort_sticky:
-    now = _lib.MAPPER_PRESORT
-  elif ratio > PRESORT_ABOVE:
-    now = _lib.MAPPER_PRESORT
-  elif ratio < DIRECT_BELOW:
-    now = _lib.MAPPER_DIRECT
-  _mapper_mode[key] = now
-
-
-def _shape_key(device, n, image_size, config, tile_rows, depth16):
-  return (device.index, int(n), int(image_size[0]), int(image_size[1]), config.tile_size,
-          None if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1])), bool(depth16))
-
-
-def _round_capacity(k: int) -> int:
-  k = max(int(k), 1)
-  return min((k + K_GRANULE - 1) // K_GRANULE * K_GRANULE, (1 << 31) - 1)
-
-
-K_PENDING = -(1 << 31)      # sentinel the host writes into the pinned word before a frame; K itself is >= 0
-
-
-class KSlots:
-  """Pinned int32 words the frames' K kernels write (``ms_frame_project_count(k_host)``), one per frame in flight.
-
-  Round 3 kept ONE word per device: a second frame enqueued before the first had looked at its overlap total (a
-  viewer thread next to a training thread, two frames rendered back to back before either is settled) reset the
-  word and the first frame then validated its capacity against the other frame's K."""
-
-  def __init__(self):
-    self.words = torch.zeros((K_SLOTS,), dtype=torch.int32).pin_memory()
-    self.view = self.words.numpy()
-    self.busy = [False] * K_SLOTS
-    self.next = 0
-    # words for frames captured into HIP graphs (kept for the life of the process: a graph replays into its word).
-    # Allocated HERE, in eager mode: pinning host memory inside a stream capture invalidates the capture
-    # (hipHostMalloc is not a capturable call — seen at 6 M gaussians, where torch's host cache had no block to reuse)
-    self.graph_words = torch.zeros((GRAPH_K_WORDS,), dtype=torch.int32).pin_memory()
-    self.graph_view = self.graph_words.numpy()
-    self.graph_next = 0
-    self.graph_free = []
-
-  def acquire_for_graph(self, state):
-    """a word for a frame being captured; it returns to the pool when the frame's state (kept alive by the graph's
-    result) is garbage collected"""
-    with _lock:
-      if self.graph_free:
-        i = self.graph_free.pop()
-      else:
-        i = self.graph_next
-        if i >= GRAPH_K_WORDS:
-          raise RuntimeError(f"more than {GRAPH_K_WORDS} live frames captured into HIP graphs in this process")
-        self.graph_next = i + 1
-    weakref.finalize(state, self.graph_free.append, i)
-    return self.graph_words[i:i + 1], self.graph_view[i:i + 1]
-
-  def acquire(self):
-    """(slot index or -1, one-element pinned tensor, its numpy view)"""
-    with _lock:
-      for _ in range(K_SLOTS):
-        i = self.next
-        self.next = (i + 1) % K_SLOTS
-        if not self.busy[i]:
-          self.busy[i] = True
-          return i, self.words[i:i + 1], self.view[i:i + 1]
-    word = torch.zeros((1,), dtype=torch.int32).pin_memory()       # more than K_SLOTS unsettled frames: a private word
-    return -1, word, word.numpy()
-
-  def release(self, i):
-    if i >= 0:
-      self.busy[i] = False
-
-
-def _k_ring(device) -> KSlots:
-  with _lock:
-    ring = _k_host.get(device.index)
-    if ring is None:
-      ring = _k_host[device.index] = KSlots()
-  return ring
-
-
-def _pinned_k(device):
-  """A pinned int32 word of its own for the frame about to be enqueued: (slot, tensor, numpy view, event, ring)"""
-  ring = _k_ring(device)
-  slot, word, view = ring.acquire()
-  return slot, word, view, torch.cuda.Event(), ring
-
-
-def _wait_for_k(k_np, k_event, at_entry=False) -> int:
-  """The host's one wait per eager frame.  Polling the pinned word the K kernel writes returns within microseconds of
-  the write; ``Event.synchronize`` (an interrupt-driven sleep) cost 0.3-0.5 ms of wake-up latency per frame, which
-  at 1 M gaussians left the GPU idle for a third of the frame."""
-  global host_syncs, entry_waits
-  deadline = time.perf_counter() + 2.0
-  spins = 0
-  while k_np[0] == K_PENDING:
-    spins += 1
-    if spins & 63 == 0:
-      time.sleep(0)                         # let other Python threads run: the poll holds the GIL otherwise
-      if time.perf_counter() > deadline:    # never seen; a lost write must not hang the caller
-        k_event.synchronize()
-        break
-  if at_entry:
-    entry_waits += 1 if spins else 0
-  else:
-    host_syncs += 1
-  return int(k_np[0])
-
-
-@contextlib.contextmanager
-def parked_gc():
-  """Run a training / timing loop with Python's cyclic collector parked.
-
-  An eager frame keeps the GPU about one frame ahead of the host (the one wait per frame is for the overlap total).
-  A generation-2 collection walks every tracked object of the process — with torch imported, 35-45 ms, i.e. ten
-  config-D frames — about once every couple of hundred frames, and the GPU idles for most of it
-  (``tools/host_overhead.py``: frame intervals median 3.40 ms, max 44 ms; 11 ms with the collector parked).
-  Reference counting still frees every tensor of a frame when the frame ends; only cycle detection is deferred to
-  the end of the block.  (A HIP-graph replay, ``FrameGraph``, needs no host per frame and is not affected.)"""
-  was_enabled = gc.isenabled()
-  gc.collect()
-  gc.freeze()
-  gc.disable()
-  try:
-    yield
-  finally:
-    gc.unfreeze()
-    if was_enabled:
-      gc.enable()
 
 
 def release_caches(force: bool = False):
@@ -307,22 +241,12 @@ def _release_caches(force: bool = False):
   would let the next replay accumulate into memory the allocator has handed to someone else; pass ``force=True`` only
   after every such graph is gone."""
   with _lock:
-    for key in list(_moments):
-      if force or key not in _moments_pinned:
-        del _moments[key]
-    if force:
-      _moments_pinned.clear()
+    release_moments(force)
     _identity.clear()
-    _stable_frames.clear()
-    _k_capacity.clear()
-    _mapper_mode.clear()
-    _presort_sticky.clear()
-    # the run words stay (4 pinned bytes per scene shape): a frame still in flight, or a captured one at every replay,
-    # writes its word — handing the memory back to the allocator would let that write land in somebody else's tensor
-    for _, view in _run_words.values():
-      view[0] = 0
-    if force:
-      _run_words.clear()
+    for key, rec in list(_shapes.items()):
+      rec.release(force)
+      if rec.run_word is None:
+        del _shapes[key]
     if force:
       _k_host.clear()          # captured graphs write their overlap totals into these pinned words
 
@@ -339,61 +263,6 @@ def identity_indexes(n: int, device) -> torch.Tensor:
   return cached
 
 
-def _moments_buffer(device, n: int, deterministic: bool) -> torch.Tensor:
-  """Persistent (n, MOMENT_ROW) accumulator of the raster backward: zero on entry of every backward pass, and zero
-  again when it returns (the per-gaussian pass clears the rows it reads) — no 64 B-per-gaussian fill per frame.
-
-  One buffer per (device, stream, size, mode): two backward passes on DIFFERENT streams never share rows (on one
-  stream they run one after the other and the rows are zero in between).  A small LRU per device instead of "one
-  size at a time": alternating two scene sizes (a 3D model and ``rasterize()`` of a 2D set) no longer reallocates and
-  zero-fills on every backward.  A buffer handed out during HIP-graph capture is pinned: its address is part of the
-  graph."""
-  stream = int(torch.cuda.current_stream(device).cuda_stream)
-  key = (device.index, stream, int(n), bool(deterministic))
-  with _lock:
-    buf = _moments.get(key)
-    if buf is None and torch.cuda.is_current_stream_capturing():
-      # a capture runs on a stream of its own: take the accumulator the eager warm-up frames of this scene size used
-      # (zero between frames) instead of allocating AND ZERO-FILLING a new one inside the graph — the fill would be
-      # replayed with every step (384 MB at 6 M gaussians)
-      for other, cand in _moments.items():
-        if (other[0], other[2], other[3]) == (key[0], key[2], key[3]):
-          buf = _moments[key] = cand
-          _moments_pinned.add(other)
-          break
-    if buf is None:
-      mine = [k for k in _moments if k[0] == device.index and k not in _moments_pinned]
-      for k in mine[:max(0, len(mine) - (MOMENTS_LRU - 1))]:
-        del _moments[k]                     # least recently used first (OrderedDict order)
-      buf = _moments[key] = torch.zeros((max(n, 1), _lib.MOMENT_ROW),
-                                        dtype=torch.int64 if deterministic else torch.float32, device=device)
-    else:
-      _moments.move_to_end(key)
-    if torch.cuda.is_current_stream_capturing():
-      _moments_pinned.add(key)
-  return buf
-
-
-def _drop_moments():
-  """After a failed backward enqueue the accumulator rows may be half-written: start from clean ones.  Buffers whose
-  address a captured HIP graph replays into are zeroed IN PLACE (freeing them would let the next replay accumulate into
-  memory the allocator has handed to someone else — what ``release_caches`` guards against with ``force``); the others
-  are dropped and reallocated on demand."""
-  with _lock:
-    for key in list(_moments):
-      if key not in _moments_pinned:
-        del _moments[key]
-        continue
-      buf = _moments[key]
-      if torch.cuda.is_current_stream_capturing():
-        continue              # (a failure inside a capture: the capture is lost anyway, and a fill must not join it)
-      # on the buffer's OWN stream (key[1]): the graph that replays into it runs there, and a fill on whatever stream
-      # is current could race with a replay in flight (ADVICE round 5)
-      own = torch.cuda.ExternalStream(key[1], device=buf.device) if key[1] else torch.cuda.default_stream(buf.device)
-      with torch.cuda.stream(own):
-        buf.zero_()
-
-
 class FrameState:
   """What one frame keeps between its forward pass, its backward pass and the lazily built ``points``."""
 
@@ -407,7 +276,8 @@ class FrameState:
     self.capacity = 0
     self.children = []            # (weakref to a tensor handed out, index list or None, 'points7' | 'colours')
     self.y0 = 0
-    self.pending = None           # eager mode: the look at K + capacity check, run once (by the frame's caller, or later)
+    self.pending = None           # eager mode: the PendingFrame = the look at K + capacity check, run once (by the frame's
+                                  # caller, or later)
     self.k_peek = None            # numpy view of the frame's pinned K word while `pending` is set
     self.consumed = False         # a backward pass was enqueued before the frame was settled
     self.key = None               # scene-shape key
@@ -497,7 +367,7 @@ class FrameState:
     return out
 
 
-def _view(block: torch.Tensor, offset: int, dtype, shape):
+def block_view(block: torch.Tensor, offset: int, dtype, shape):
   count = 1
   for s in shape:
     count *= s
@@ -505,105 +375,108 @@ def _view(block: torch.Tensor, offset: int, dtype, shape):
   return block[offset:offset + nbytes].view(dtype).view(*shape)
 
 
+def byte_block(nbytes, device):
+  return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
+
+
+def frame_desc(n, image_size, dtype, f, sh_degree, config, depth_range=(0.0, 0.0), tile_rows=None, projected=False,
+               capacity=0, depth16=False):
+  """(ms_frame_desc of a frame, the tile rows it renders)"""
+  w, h = int(image_size[0]), int(image_size[1])
+  ts = config.tile_size
+  tiles_high = (h + ts - 1) // ts
+  rows = (0, tiles_high) if tile_rows is None else (max(0, int(tile_rows[0])), min(tiles_high, int(tile_rows[1])))
+  return _lib.FrameDescC(n=int(n), k_capacity=int(capacity), image_w=w, image_h=h, dtype=_lib.dtype_code(dtype), f=int(f),
+                         sh_degree=int(sh_degree), depth16=int(depth16), tile_row_begin=rows[0], tile_row_end=rows[1],
+                         projected_input=int(projected), mapper=0, near_plane=float(depth_range[0]),
+                         far_plane=float(depth_range[1]), blur_cov=float(config.blur_cov),
+                         clamp_margin=float(config.clamp_margin), raster=_lib.raster_config_c(config)), rows
+
+
+def frame_layout(desc, what="frame layout"):
+  lay = _lib.FrameLayoutC()
+  _lib.check(_lib.load().ms_frame_layout_query(ctypes.byref(desc), ctypes.byref(lay)), what)
+  return lay
+
+
+def _point_outputs(n, config, dtype, device):
+  """visibility (n,) and point heuristic (n, 2) of a frame, zero; without rows when the config does not ask for them"""
+  return (torch.zeros((n if config.compute_visibility else 0,), dtype=dtype, device=device),
+          torch.zeros((n if config.compute_point_heuristic else 0, 2), dtype=dtype, device=device))
+
+
+def backward_mode(desc):
+  """(whether the raster backward of this frame accumulates moment rows, whether it commits them deterministically:
+  ``rasterizer.function.DETERMINISTIC_BACKWARD`` / MS_DETERMINISTIC)"""
+  from .rasterizer import function as raster_function
+  det = bool(raster_function.DETERMINISTIC_BACKWARD)
+  return bool(_lib.load().ms_frame_uses_moments(ctypes.byref(desc), int(det))), det
+
+
+def attach_moments(gr, g_image, device, n, det):
+  """Point the grads struct of a moments-path backward at its accumulator; returns what must stay alive until the launch"""
+  gr.moments = _moments_buffer(device, n, det).data_ptr()
+  gr.deterministic = int(det)
+  if not det:
+    return None
+  fixed_exp = _lib.fixed_point_exponents(g_image)
+  gr.fixed_exp = fixed_exp.data_ptr()
+  return fixed_exp
+
+
+def _enqueue_backward(state, gr, device, what):
+  try:
+    with _lock:       # the two launches of a backward pass are enqueued back to back (ctypes releases the GIL)
+      _lib.check(_lib.load().ms_frame_backward(ctypes.byref(state.desc), ctypes.byref(state.inputs), state.keep_n.data_ptr(),
+                                               state.keep_k.data_ptr(), ctypes.byref(gr), _lib.current_stream(device)), what)
+  except Exception:
+    _drop_moments()         # the accumulator rows may have been left half-written: start from a fresh buffer
+    raise
+
+
 def _strip_pixels(rows, tile_size, h):
   return min(rows[0] * tile_size, h), min(rows[1] * tile_size, h)
 
 
-def _enqueue_forward(desc, inputs, keep_n, scratch_n, key, image_ptr, alpha_ptr, visibility, device, what, state,
-                     settle_now=False):
-  """The two forward calls of the executor plus the eager-mode capacity policy: everything is enqueued with the
-  remembered capacity BEFORE the host looks at the overlap total (a pinned word the K kernel writes), and the emission
-  is re-run with larger buffers in the rare case it did not fit.  Fills ``state`` (layout, keep_k, capacity, k) and
-  leaves ``state.pending`` = the settle step (the wait + check) for the caller to run as the LAST thing it does for
-  this frame — the later the host looks, the more of its own per-frame work is hidden behind queued GPU work."""
-  lib = _lib.load()
-  stream = _lib.current_stream(device)
-  capturing = torch.cuda.is_current_stream_capturing()
-  if not capturing:
-    settle_all()                 # earlier frames of this process: their words are (almost always) written long ago
-  # the scene-shape caches are shared by every thread that renders (a viewer next to a trainer): looked up and updated
-  # under the lock (ADVICE round 4)
-  with _lock:
-    capacity = _k_capacity.get(key, 0)
-    # what the per-tile sort of an earlier frame of this shape reported (no synchronisation: the word is a frame or two old)
-    run_word = _run_words.get(key)
-    if run_word is None and not capturing:
-      t = torch.zeros((1,), dtype=torch.int32).pin_memory()
-      run_word = _run_words[key] = (t, t.numpy())
-    if run_word is not None:
-      if int(run_word[1][0]) > LONG_RUN_LIMIT and key not in _presort_sticky:
-        _presort_sticky.add(key)
-        _mapper_mode[key] = _lib.MAPPER_PRESORT
-      inputs.longest_run_host = run_word[0].data_ptr()
-    # the same in every call of this frame.  The FIRST frame of a scene shape (nothing known about how its overlaps are
-    # spread) takes the sequence whose cost does not depend on that — the pre-sort, 0.1-0.2 ms dearer on a scene like
-    # config D — and carries the segment launches: a pile-up then costs its first frame what it costs every frame, not
-    # the 7 ms of ONE workgroup sorting a 244 000-entry run plus one workgroup rasterizing it (round 5's first frame of
-    # that shape: 11.1 ms against 1.67 steady; tools/sweep_scenes.py guards first <= 3 x steady).  The second frame
-    # runs what _choose_mapper settled on.
-    first_of_shape = key not in _mapper_mode
-    desc.mapper = _mapper_mode.get(key, _lib.MAPPER_PRESORT)
-    # a shape that showed a run above LONG_RUN_LIMIT also has its long runs rasterized in segments (the raster forward
-    # reports such runs through the same word on either mapper sequence)
-    # (field value 1 = the default threshold, > 1 = the threshold itself; the library raises thresholds below 256)
-    split_on = SPLIT_LONG_RUNS and (SPLIT_ALWAYS or first_of_shape or key in _presort_sticky)
-    desc.split_long_runs = (max(2, SPLIT_MIN_RUN) if SPLIT_MIN_RUN > 0 else 1) if split_on else 0
-    desc.split_seg_len = SPLIT_SEG_LEN
-  if capturing and capacity == 0:
-    raise RuntimeError(f"{what} under HIP-graph capture: the overlap-list capacity of this scene shape is unknown; "
-                       "render one eager frame first or call frame.set_overlap_capacity(...)")
-  if capturing:
-    # a pinned word of the captured frame's own: every replay writes its overlap total there, so the host can tell
-    # an overflowed replay (background-only image, zero gradients) WITHOUT touching the device — see check_replays()
-    slot, ring, k_event = -1, None, None
-    k_word, k_np = _k_ring(device).acquire_for_graph(state)      # pinned in eager mode already (the warm-up frames)
-    k_np[0] = 0
-    state.k_word, state.k_view, state.captured = k_word, k_np, True
-    _captured_frames.append(weakref.ref(state))
-  else:
-    slot, k_word, k_np, k_event, ring = _pinned_k(device)
-    k_np[0] = K_PENDING
-  try:
-    _lib.check(lib.ms_frame_project_count(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), scratch_n.data_ptr(),
-                                          k_word.data_ptr(), None, stream), what)
-  except Exception:
-    if ring is not None:
-      ring.release(slot)
-    raise
-  if not capturing:
-    k_event.record(torch.cuda.current_stream(device))
-  if (capturing and SH_SIDE_STREAM and desc.sh_degree >= 0 and not desc.projected_input and desc.n > 0
-      and os.environ.get('MS_SPLAT_ROWS', '0') != '1'):
-    main = torch.cuda.current_stream(device)
-    with _lock:
-      side = _side_streams.get(device.index)
-      if side is None:
-        side = _side_streams[device.index] = torch.cuda.Stream(device=device)
-    side.wait_stream(main)                # behind the projection (and the overlap count and scan enqueued with it)
-    _lib.check(lib.ms_frame_sh_colours(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), side.cuda_stream), what)
-    state.colours_ready = torch.cuda.Event()
-    state.colours_ready.record(side)
-    inputs.colours_ready_event = int(state.colours_ready.cuda_event)
+class PendingFrame:
+  """What an enqueued frame owns until the host has looked at its overlap total: the arguments of its map + raster call
+  (run again with larger buffers when the total did not fit) and, in eager mode, its pinned K word.  Calling it is the
+  settle step; ``FrameState.pending`` holds it until then, and whoever takes it from there (under ``_lock``) runs it."""
 
-  def map_raster(cap):
+  def __init__(self, state, desc, inputs, scratch_n, image_ptr, alpha_ptr, visibility, device, what):
+    self.state, self.desc, self.inputs, self.scratch_n = state, desc, inputs, scratch_n
+    self.image_ptr, self.alpha_ptr, self.device, self.what = image_ptr, alpha_ptr, device, what
+    self.stream = _lib.current_stream(device)      # a re-run is enqueued where the frame was
+    self.visibility = visibility       # re-zeroed before a re-run (None: the frame computes none in its forward)
+    self.ring, self.slot = None, -1    # eager mode: the ring the frame's K word is from (slot -1: a private word)
+    self.k_word = self.k_np = self.k_event = None
+
+  def acquire_k(self):
+    self.ring = k_ring(self.device)
+    self.slot, self.k_word, self.k_np = self.ring.acquire()
+    self.k_event = torch.cuda.Event()
+    self.k_np[0] = K_PENDING
+
+  def release_k(self):
+    """this frame's word may serve another frame from here on"""
+    ring, self.ring = self.ring, None
+    if ring is not None:
+      ring.release(self.slot)
+
+  def map_raster(self, cap):
+    state, desc = self.state, self.desc
     desc.k_capacity = cap
-    lay = _lib.FrameLayoutC()
-    _lib.check(lib.ms_frame_layout_query(ctypes.byref(desc), ctypes.byref(lay)), what)
-    keep_k = torch.empty((lay.keep_k_bytes,), dtype=torch.uint8, device=device)
-    scratch_k = torch.empty((lay.scratch_k_bytes,), dtype=torch.uint8, device=device)
-    _lib.check(lib.ms_frame_map_raster(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), scratch_n.data_ptr(),
-                                       keep_k.data_ptr(), scratch_k.data_ptr(), image_ptr, alpha_ptr,
-                                       _lib.ptr(visibility), stream), what)
+    lay = frame_layout(desc, self.what)
+    keep_k, scratch_k = byte_block(lay.keep_k_bytes, self.device), byte_block(lay.scratch_k_bytes, self.device)
+    _lib.check(_lib.load().ms_frame_map_raster(ctypes.byref(desc), ctypes.byref(self.inputs), state.keep_n.data_ptr(),
+                                               self.scratch_n.data_ptr(), keep_k.data_ptr(), scratch_k.data_ptr(),
+                                               self.image_ptr, self.alpha_ptr, _lib.ptr(self.visibility),
+                                               self.stream), self.what)
     state.layout, state.keep_k, state.capacity = lay, keep_k, cap
 
-  state.k, state.pending = None, None
-  state.key = key
-  if capturing:
-    map_raster(capacity)
-    return
-
-  def settle(at_entry=False):
-    global settles
+  def __call__(self, at_entry=False):
+    global settles, host_syncs, entry_waits
+    state, what = self.state, self.what
     state.pending = None
     state.k_peek = None
     with _lock:
@@ -612,18 +485,20 @@ def _enqueue_forward(desc, inputs, keep_n, scratch_n, key, image_ptr, alpha_ptr,
       except ValueError:
         pass
     try:
-      k_total = _wait_for_k(k_np, k_event, at_entry)
+      k_total, waited = wait_for_k(self.k_np, self.k_event)
     finally:
-      ring.release(slot)        # this frame's word may serve another frame from here on
+      self.release_k()
+    if at_entry:
+      entry_waits += 1 if waited else 0
+    else:
+      host_syncs += 1
     settles += 1
     if k_total < 0:
       raise OverflowError(f"{what}: more than 2^31 - 1 tile overlaps (the overlap index is int32 like the "
                           "reference's, tile_mapper.py:150); use a larger tile size or fewer / smaller gaussians")
     overflowed = state.capacity == 0 or k_total > state.capacity
     with _lock:
-      _k_capacity[key] = max(_k_capacity.get(key, 0), _round_capacity(k_total * K_SLACK))
-      _choose_mapper(key, k_total, desc.n)
-      _stable_frames[key] = 0 if overflowed else _stable_frames.get(key, 0) + 1
+      shape_record(state.key, create=True).observe(k_total, self.desc.n, overflowed)
     if overflowed and state.consumed:
       # found too late: the backward of this frame ran on the empty lists of the overflowed forward
       raise FrameOverflow(
@@ -632,21 +507,73 @@ def _enqueue_forward(desc, inputs, keep_n, scratch_n, key, image_ptr, alpha_ptr,
         "only and returned zero gradients.  The capacity has been raised for the next frame; set MS_STRICT=1 (or "
         "frame.LAZY_SETTLE = False) to make every frame wait for its overlap total before it returns.")
     if overflowed:
-      if visibility is not None and k_total > 0:
-        visibility.zero_()
-      map_raster(_round_capacity(k_total * K_SLACK))
+      if self.visibility is not None and k_total > 0:
+        self.visibility.zero_()
+      self.map_raster(round_capacity(k_total * K_SLACK))
     state.k = k_total
 
-  state.capacity = 0
-  if capacity > 0:
-    try:
-      map_raster(capacity)        # everything is enqueued before the host looks at K
-    except Exception:
-      ring.release(slot)          # (an allocation failure here must not leave the frame's K word busy for ever)
-      raise
-  state.pending, state.k_peek = settle, k_np
+
+def _enqueue_forward(desc, inputs, key, image_ptr, alpha_ptr, visibility, device, what, state, settle_now=False):
+  """The two forward calls of the executor plus the eager-mode capacity policy: everything is enqueued with the
+  remembered capacity BEFORE the host looks at the overlap total (a pinned word the K kernel writes), and the emission
+  is re-run with larger buffers in the rare case it did not fit.  Fills ``state`` (keep_n, layout, keep_k, capacity, k)
+  and leaves ``state.pending`` = the settle step (the wait + check) for the caller to run as the LAST thing it does for
+  this frame — the later the host looks, the more of its own per-frame work is hidden behind queued GPU work."""
+  lib = _lib.load()
+  capturing = torch.cuda.is_current_stream_capturing()
+  if not capturing:
+    settle_all()                 # earlier frames of this process: their words are (almost always) written long ago
+  with _lock:
+    capacity, desc.mapper, desc.split_long_runs, desc.split_seg_len, run_word = shape_record(key, create=True).plan(
+      capturing, SPLIT_LONG_RUNS, SPLIT_ALWAYS, SPLIT_MIN_RUN, SPLIT_SEG_LEN)
+  if run_word is not None:
+    inputs.longest_run_host = run_word
+  if capturing and capacity == 0:
+    raise RuntimeError(f"{what} under HIP-graph capture: the overlap-list capacity of this scene shape is unknown; "
+                       "render one eager frame first or call frame.set_overlap_capacity(...)")
+  desc.k_capacity = capacity
+  layout = frame_layout(desc, what)
+  keep_n, scratch_n = byte_block(layout.keep_n_bytes, device), byte_block(layout.scratch_n_bytes, device)
+  state.desc, state.inputs, state.keep_n, state.key = desc, inputs, keep_n, key
+  state.k, state.pending, state.capacity = None, None, 0
+  pending = PendingFrame(state, desc, inputs, scratch_n, image_ptr, alpha_ptr, visibility, device, what)
+  if capturing:
+    # a pinned word of the captured frame's own: every replay writes its overlap total there, so the host can tell
+    # an overflowed replay (background-only image, zero gradients) WITHOUT touching the device — see check_replays()
+    k_word, k_np = k_ring(device).acquire_for_graph(state)       # pinned in eager mode already (the warm-up frames)
+    k_np[0] = 0
+    state.k_word, state.k_view, state.captured = k_word, k_np, True
+    _captured_frames.append(weakref.ref(state))
+  else:
+    pending.acquire_k()
+    k_word = pending.k_word
+  try:
+    _lib.check(lib.ms_frame_project_count(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), scratch_n.data_ptr(),
+                                          k_word.data_ptr(), None, pending.stream), what)
+    if not capturing:
+      pending.k_event.record(torch.cuda.current_stream(device))
+    elif (SH_SIDE_STREAM and desc.sh_degree >= 0 and not desc.projected_input and desc.n > 0
+          and os.environ.get('MS_SPLAT_ROWS', '0') != '1'):
+      main = torch.cuda.current_stream(device)
+      with _lock:
+        side = _side_streams.get(device.index)
+        if side is None:
+          side = _side_streams[device.index] = torch.cuda.Stream(device=device)
+      side.wait_stream(main)                # behind the projection (and the overlap count and scan enqueued with it)
+      _lib.check(lib.ms_frame_sh_colours(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), side.cuda_stream), what)
+      state.colours_ready = torch.cuda.Event()
+      state.colours_ready.record(side)
+      inputs.colours_ready_event = int(state.colours_ready.cuda_event)
+    if capacity > 0:
+      pending.map_raster(capacity)        # everything is enqueued before the host looks at K
+  except Exception:
+    pending.release_k()                   # (a failure here must not leave the frame's K word busy for ever)
+    raise
+  if capturing:
+    return
+  state.pending, state.k_peek = pending, pending.k_np
   if capacity == 0 or settle_now:
-    settle()
+    state.settle()                      # a shape with unknown capacity settles at once
 
 
 def settle_all():
@@ -656,16 +583,27 @@ def settle_all():
       if not _unsettled:
         return
       st = _unsettled[0]
-    with _lock:
       fn, st.pending = st.pending, None
-      if fn is None and _unsettled and _unsettled[0] is st:
+      if fn is None:
         _unsettled.popleft()     # (settled by somebody else in the meantime)
     if fn is not None:
       fn(True)                   # removes itself from the queue first thing
 
 
+def _settle_or_queue(state, differentiated: bool):
+  """The host's look at the overlap total: last, behind everything it had to do anyway — or, for a frame that is about to
+  be differentiated on a scene shape with a settled capacity, not before the next frame (LAZY_SETTLE)"""
+  if differentiated and state.pending is not None and state.key is not None and lazy_settle_allowed(state.key):
+    state.lazy = True
+    with _lock:
+      _unsettled.append(state)     # looked at by the next frame's entry (settle_all) or the first host access
+  else:
+    state.settle()
+
+
 def lazy_settle_allowed(key) -> bool:
-  return LAZY_SETTLE and not STRICT and _stable_frames.get(key, 0) >= LAZY_AFTER
+  rec = _shapes.get(key)
+  return LAZY_SETTLE and not STRICT and rec is not None and rec.stable >= LAZY_AFTER
 
 
 _captured_frames = []      # weak references to the FrameStates of frames captured into HIP graphs
@@ -728,7 +666,6 @@ class _FrameFunction(torch.autograd.Function):
     n = pos.shape[0]
     w, h = int(opts.image_size[0]), int(opts.image_size[1])
     ts = config.tile_size
-    tiles_high = (h + ts - 1) // ts
 
     if opts.use_sh:
       assert feat.ndim == 3, f"SH features must have 3 dimensions, got {feat.shape}"
@@ -740,18 +677,9 @@ class _FrameFunction(torch.autograd.Function):
       assert feat.ndim == 2, f"Features must be (N, C) if use_sh=False, got {feat.shape}"
       f, degree = feat.shape[1], -1
 
-    rows = (0, tiles_high) if opts.tile_rows is None else (max(0, int(opts.tile_rows[0])), min(tiles_high, int(opts.tile_rows[1])))
     key = _shape_key(device, n, (w, h), config, opts.tile_rows, opts.use_depth16)
-    desc = _lib.FrameDescC(n=n, k_capacity=_k_capacity.get(key, 0), image_w=w, image_h=h, dtype=_lib.dtype_code(dtype), f=f,
-                           sh_degree=degree, depth16=int(opts.use_depth16), tile_row_begin=rows[0], tile_row_end=rows[1],
-                           projected_input=0, mapper=0, near_plane=float(opts.depth_range[0]),
-                           far_plane=float(opts.depth_range[1]), blur_cov=float(config.blur_cov),
-                           clamp_margin=float(config.clamp_margin), raster=_lib.raster_config_c(config))
-    layout = _lib.FrameLayoutC()
-    _lib.check(lib.ms_frame_layout_query(ctypes.byref(desc), ctypes.byref(layout)), "render_gaussians")
+    desc, rows = frame_desc(n, (w, h), dtype, f, degree, config, opts.depth_range, opts.tile_rows, depth16=opts.use_depth16)
     stream = _lib.current_stream(device)
-    keep_n = torch.empty((layout.keep_n_bytes,), dtype=torch.uint8, device=device)
-    scratch_n = torch.empty((layout.scratch_n_bytes,), dtype=torch.uint8, device=device)
     inputs = _lib.FrameInputsC(position=pos.data_ptr(), log_scaling=lsc.data_ptr(), rotation=rot.data_ptr(),
                                alpha_logit=alog.data_ptr(), feature=feat.data_ptr(), T_camera_world=Tcw.data_ptr(),
                                projection=proj.data_ptr(), points7=None, depth=None, colours=None)
@@ -761,12 +689,12 @@ class _FrameFunction(torch.autograd.Function):
     y0, y1 = _strip_pixels(rows, ts, h) if opts.crop_to_rows else (0, h)
     image = torch.empty((y1 - y0, w, f), dtype=dtype, device=device)
     alpha = torch.empty((y1 - y0, w), dtype=dtype, device=device)
-    if not opts.crop_to_rows and rows != (0, tiles_high):
+    whole = rows == (0, (h + ts - 1) // ts)
+    if not opts.crop_to_rows and not whole:
       image.zero_(); alpha.zero_()
-    visibility = torch.zeros((n,), dtype=dtype, device=device) if config.compute_visibility else torch.empty((0,), dtype=dtype, device=device)
-    heuristic = torch.zeros((n, 2), dtype=dtype, device=device) if config.compute_point_heuristic else torch.empty((0, 2), dtype=dtype, device=device)
+    visibility, heuristic = _point_outputs(n, config, dtype, device)
     es = image.element_size()
-    state.desc, state.inputs, state.keep_n, state.y0 = desc, inputs, keep_n, y0
+    state.y0 = y0
     state.tensors = tensors                                  # the pointers in `inputs` stay valid
     if y1 > y0:
       image_ptr, alpha_ptr = image.data_ptr() - y0 * w * f * es, alpha.data_ptr() - y0 * w * es
@@ -779,14 +707,14 @@ class _FrameFunction(torch.autograd.Function):
     defer_vis = bool(state.vis_deferred and config.compute_visibility and config.compute_point_heuristic and n > 0
                      and lib.ms_frame_uses_moments(ctypes.byref(desc), 0))
     state.vis_deferred, state.vis_ready = defer_vis, not defer_vis
-    _enqueue_forward(desc, inputs, keep_n, scratch_n, key, image_ptr, alpha_ptr,
+    _enqueue_forward(desc, inputs, key, image_ptr, alpha_ptr,
                      visibility if config.compute_visibility and not defer_vis else None, device,
                      "render_gaussians", state, settle_now=opts.render_median_depth)
-    layout = state.layout
+    layout, keep_n = state.layout, state.keep_n
 
-    points7 = _view(keep_n, layout.points7, dtype, (n, 7))
-    depth = _view(keep_n, layout.depth, dtype, (n,))
-    colours = _view(keep_n, layout.colours, dtype, (n, f)) if opts.use_sh else None
+    points7 = block_view(keep_n, layout.points7, dtype, (n, 7))
+    depth = block_view(keep_n, layout.depth, dtype, (n,))
+    colours = block_view(keep_n, layout.colours, dtype, (n, f)) if opts.use_sh else None
     if defer_vis:
       state.vis_args = (visibility.detach(), points7.detach(), (colours if opts.use_sh else feat).detach(), w, h, f, rows,
                         y0, y1, config)
@@ -798,7 +726,7 @@ class _FrameFunction(torch.autograd.Function):
                                            compute_visibility=False, compute_point_heuristic=False))
       median = torch.empty((y1 - y0, w, 1), dtype=dtype, device=device)
       median_alpha = torch.empty((y1 - y0, w), dtype=dtype, device=device)
-      if not opts.crop_to_rows and rows != (0, tiles_high):
+      if not opts.crop_to_rows and not whole:
         median.zero_()
       if y1 > y0:
         _lib.check(lib.ms_raster_fwd(points7.data_ptr(), depth.data_ptr(), state.tile_ranges().data_ptr(),
@@ -818,7 +746,6 @@ class _FrameFunction(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, g_image, g_alpha, g_points7, g_depth, g_colours, g_vis, g_heur, g_median):
-    from .rasterizer import function as raster_function
     lib = _lib.load()
     pos, lsc, rot, alog, feat, Tcw, proj, image = ctx.saved_tensors
     state, opts = ctx.state, ctx.opts
@@ -836,8 +763,7 @@ class _FrameFunction(torch.autograd.Function):
 
     w, h = opts.image_size
     stream = _lib.current_stream(device)
-    det = bool(raster_function.DETERMINISTIC_BACKWARD)
-    moments_path = bool(lib.ms_frame_uses_moments(ctypes.byref(desc), int(det)))
+    moments_path, det = backward_mode(desc)
     # dL/dimage of a sum / mean loss arrives as an EXPANDED scalar (strides 0): the moments kernel reads one pixel's f
     # values instead of an (H, W, f) copy that .contiguous() would write and the kernel read back (50 MB at 2048^2)
     broadcast = (BROADCAST_GRAD and moments_path and g_image is not None and g_image.dim() == 3 and g_image.shape[0] * g_image.shape[1] > 1
@@ -867,14 +793,8 @@ class _FrameFunction(torch.autograd.Function):
         setattr(gr, name, g.data_ptr())
 
     grad_points7 = grad_colours = None
-    fixed_exp = None
     if moments_path:
-      moments = _moments_buffer(device, n, det)
-      gr.moments = moments.data_ptr()
-      gr.deterministic = int(det)
-      if det:
-        fixed_exp = _lib.fixed_point_exponents(g_image)
-        gr.fixed_exp = fixed_exp.data_ptr()
+      fixed_exp = attach_moments(gr, g_image, device, n, det)      # noqa: F841 (alive until the launch)
       if want_points:
         grad_points7 = torch.empty((n, 7), dtype=dtype, device=device)
       if want_colours:
@@ -904,13 +824,7 @@ class _FrameFunction(torch.autograd.Function):
     elif state.vis_deferred:
       state.ensure_visibility()           # (a backward that cannot deliver it: not on the moments path after all)
 
-    try:
-      with _lock:       # the two launches of a backward pass are enqueued back to back (ctypes releases the GIL)
-        _lib.check(lib.ms_frame_backward(ctypes.byref(desc), ctypes.byref(state.inputs), state.keep_n.data_ptr(),
-                                         state.keep_k.data_ptr(), ctypes.byref(gr), stream), "render_gaussians backward")
-    except Exception:
-      _drop_moments()         # the accumulator rows may have been left half-written: start from a fresh buffer
-      raise
+    _enqueue_backward(state, gr, device, "render_gaussians backward")
     if vis_here and not state.vis_ready:
       state.vis_ready = True
 
@@ -937,7 +851,7 @@ class _FrameFunction(torch.autograd.Function):
           # dL/dT = -A^T (dL/dA) A^T with dL/dA non-zero in A[:3, 3] only
           total_c = grad_colours if (moments_path or g_colours is None) else grad_colours + g_colours
           g_cam = torch.zeros((3,), dtype=dtype, device=device)
-          cam_pos = _view(state.keep_n, state.layout.camera_position, dtype, (3,))
+          cam_pos = block_view(state.keep_n, state.layout.camera_position, dtype, (3,))
           _lib.check(lib.ms_sh_bwd(feat.data_ptr(), pos.data_ptr(), identity_indexes(n, device).data_ptr(), cam_pos.data_ptr(),
                                    n, f, ctx.degree, None, total_c.data_ptr(), None, None, g_cam.data_ptr(), 0,
                                    _lib.dtype_code(dtype), stream), "render_gaussians backward (camera position)")
@@ -957,7 +871,6 @@ class _RasterizeFrameFunction(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, gaussians2d, depth, features, image_size, config, use_depth16, state):
-    lib = _lib.load()
     _lib.require_gpu(gaussians2d, depth, features)
     assert gaussians2d.ndim == 2 and gaussians2d.shape[1] == 7, f"gaussians2d must be (N, 7), got {gaussians2d.shape}"
     assert features.ndim == 2 and features.shape[0] == gaussians2d.shape[0], \
@@ -970,22 +883,13 @@ class _RasterizeFrameFunction(torch.autograd.Function):
     n, f = feats.shape
     w, h = int(image_size[0]), int(image_size[1])
     key = ('2d',) + _shape_key(device, n, (w, h), config, None, use_depth16)
-    desc = _lib.FrameDescC(n=n, k_capacity=_k_capacity.get(key, 0), image_w=w, image_h=h, dtype=_lib.dtype_code(dtype), f=f,
-                           sh_degree=-1, depth16=int(use_depth16), tile_row_begin=0, tile_row_end=1 << 30,
-                           projected_input=1, mapper=0, near_plane=0.0, far_plane=0.0, blur_cov=0.0, clamp_margin=0.0,
-                           raster=_lib.raster_config_c(config))
-    layout = _lib.FrameLayoutC()
-    _lib.check(lib.ms_frame_layout_query(ctypes.byref(desc), ctypes.byref(layout)), "rasterize")
-    keep_n = torch.empty((layout.keep_n_bytes,), dtype=torch.uint8, device=device)
-    scratch_n = torch.empty((layout.scratch_n_bytes,), dtype=torch.uint8, device=device)
+    desc, _ = frame_desc(n, (w, h), dtype, f, -1, config, projected=True, depth16=use_depth16)
     inputs = _lib.FrameInputsC(points7=p.data_ptr(), depth=d.data_ptr(), colours=feats.data_ptr())
     image = torch.empty((h, w, f), dtype=dtype, device=device)
     alpha = torch.empty((h, w), dtype=dtype, device=device)
-    visibility = torch.zeros((n,), dtype=dtype, device=device) if config.compute_visibility else torch.empty((0,), dtype=dtype, device=device)
-    heuristic = torch.zeros((n, 2), dtype=dtype, device=device) if config.compute_point_heuristic else torch.empty((0, 2), dtype=dtype, device=device)
-    state.desc, state.inputs, state.keep_n = desc, inputs, keep_n
+    visibility, heuristic = _point_outputs(n, config, dtype, device)
     state.tensors = (p, d, feats)
-    _enqueue_forward(desc, inputs, keep_n, scratch_n, key, image.data_ptr(), alpha.data_ptr(),
+    _enqueue_forward(desc, inputs, key, image.data_ptr(), alpha.data_ptr(),
                      visibility if config.compute_visibility else None, device, "rasterize", state)
     ctx.set_materialize_grads(False)
     ctx.state, ctx.config, ctx.size, ctx.heuristic = state, config, (w, h), heuristic
@@ -995,8 +899,6 @@ class _RasterizeFrameFunction(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, g_image, g_alpha, g_heur, g_vis):
-    from .rasterizer import function as raster_function
-    lib = _lib.load()
     p, feats, image = ctx.saved_tensors
     state, config = ctx.state, ctx.config
     state.settle_if_known()
@@ -1008,8 +910,7 @@ class _RasterizeFrameFunction(torch.autograd.Function):
     device, dtype = p.device, p.dtype
     if n == 0:
       return torch.zeros_like(p), None, torch.zeros_like(feats), None, None, None, None
-    det = bool(raster_function.DETERMINISTIC_BACKWARD)
-    moments_path = bool(lib.ms_frame_uses_moments(ctypes.byref(state.desc), int(det)))
+    moments_path, det = backward_mode(state.desc)
     make = torch.empty if moments_path else torch.zeros        # the finalize pass stores, the generic kernels accumulate
     gp = make((n, 7), dtype=dtype, device=device)
     gf = make((n, f), dtype=dtype, device=device)
@@ -1017,23 +918,11 @@ class _RasterizeFrameFunction(torch.autograd.Function):
     gr = _lib.FrameGradsC()
     gr.image, gr.grad_image = image.data_ptr(), g_image.data_ptr()
     gr.grad_points7, gr.grad_colours = gp.data_ptr(), gf.data_ptr()
-    fixed_exp = None
     if moments_path:
-      gr.moments = _moments_buffer(device, n, det).data_ptr()
-      gr.deterministic = int(det)
-      if det:
-        fixed_exp = _lib.fixed_point_exponents(g_image)
-        gr.fixed_exp = fixed_exp.data_ptr()
+      fixed_exp = attach_moments(gr, g_image, device, n, det)      # noqa: F841 (alive until the launch)
     if heuristic is not None:
       gr.point_heuristic = heuristic.data_ptr()
-    try:
-      with _lock:
-        _lib.check(lib.ms_frame_backward(ctypes.byref(state.desc), ctypes.byref(state.inputs), state.keep_n.data_ptr(),
-                                         state.keep_k.data_ptr(), ctypes.byref(gr), _lib.current_stream(device)),
-                   "rasterize backward")
-    except Exception:
-      _drop_moments()
-      raise
+    _enqueue_backward(state, gr, device, "rasterize backward")
     return (gp if need_points else None), None, (gf if need_features else None), None, None, None, None
 
 
@@ -1042,12 +931,7 @@ def rasterize_frame(gaussians2d, depth, features, image_size, config: RasterConf
   state = FrameState()
   out = _RasterizeFrameFunction.apply(gaussians2d, depth, features, tuple(int(x) for x in image_size), config,
                                       bool(use_depth16), state)
-  if out[0].requires_grad and state.pending is not None and state.key is not None and lazy_settle_allowed(state.key):
-    state.lazy = True
-    with _lock:
-      _unsettled.append(state)
-  else:
-    state.settle()
+  _settle_or_queue(state, out[0].requires_grad)
   return out
 
 
@@ -1115,14 +999,7 @@ def render_frame(gaussians, camera_params, config: RasterConfig, use_sh: bool, u
   rendering = Rendering(image=image, image_weight=alpha, depth_image=None, median_depth_image=median, points=points,
                         camera=camera_params, config=config)
   object.__setattr__(rendering, 'frame', state)
-  # the host's look at the overlap total: last, behind everything it had to do anyway — or, for a frame that is about to
-  # be differentiated on a scene shape with a settled capacity, not before the next frame (LAZY_SETTLE)
-  if image.requires_grad and state.pending is not None and state.key is not None and lazy_settle_allowed(state.key):
-    state.lazy = True
-    with _lock:
-      _unsettled.append(state)     # looked at by the next frame's entry (settle_all) or the first host access
-  else:
-    state.settle()
+  _settle_or_queue(state, image.requires_grad)
   return rendering
 
 

@@ -92,29 +92,6 @@ class StageTimer:
     return {k: round(v / max(self.steps, 1), 4) for k, v in self.totals.items()}
 
 
-def _desc(n, image_size, dtype, f, sh_degree, config, depth_range, tile_rows=None, projected=False, capacity=0,
-          depth16=False):
-  w, h = int(image_size[0]), int(image_size[1])
-  ts = config.tile_size
-  tiles_high = (h + ts - 1) // ts
-  rows = (0, tiles_high) if tile_rows is None else (max(0, int(tile_rows[0])), min(tiles_high, int(tile_rows[1])))
-  return _lib.FrameDescC(n=int(n), k_capacity=int(capacity), image_w=w, image_h=h, dtype=_lib.dtype_code(dtype), f=int(f),
-                         sh_degree=int(sh_degree), depth16=int(depth16), tile_row_begin=rows[0], tile_row_end=rows[1],
-                         projected_input=int(projected), mapper=0, near_plane=float(depth_range[0]),
-                         far_plane=float(depth_range[1]), blur_cov=float(config.blur_cov),
-                         clamp_margin=float(config.clamp_margin), raster=_lib.raster_config_c(config)), rows
-
-
-def _layout(desc):
-  lay = _lib.FrameLayoutC()
-  _lib.check(_lib.load().ms_frame_layout_query(ctypes.byref(desc), ctypes.byref(lay)), "frame layout")
-  return lay
-
-
-def _block(nbytes, device):
-  return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
-
-
 def _feature_shape(feature: torch.Tensor, use_sh: bool):
   if use_sh:
     assert feature.ndim == 3, f"SH features must have 3 dimensions, got {feature.shape}"
@@ -178,9 +155,9 @@ class _RankStep:
       self.mapper = _lib.MAPPER_PRESORT
     desc.mapper = self.mapper
     inputs.longest_run_host = self.run_word.data_ptr()
-    lay = _layout(desc)
-    keep_n, scratch_n = _block(lay.keep_n_bytes, device), _block(lay.scratch_n_bytes, device)
-    keep_k, scratch_k = _block(lay.keep_k_bytes, device), _block(lay.scratch_k_bytes, device)
+    lay = frame.frame_layout(desc)
+    keep_n, scratch_n = frame.byte_block(lay.keep_n_bytes, device), frame.byte_block(lay.scratch_n_bytes, device)
+    keep_k, scratch_k = frame.byte_block(lay.keep_k_bytes, device), frame.byte_block(lay.scratch_k_bytes, device)
     _lib.check(lib.ms_frame_project_count(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), scratch_n.data_ptr(),
                                           self.k_word.data_ptr(), None, stream), "rank step (map)")
     w = self.image_size[0]
@@ -273,19 +250,13 @@ class _RankStep:
       torch.cuda.synchronize()
       self.poll()
 
-  def _raster_backward_mode(self, lib, desc, gr, g_image, device, rows_n):
+  def _raster_backward_mode(self, desc, gr, g_image, device, rows_n):
     """moments path + deterministic commits as frame.py does it (``rasterizer.function.DETERMINISTIC_BACKWARD`` /
     MS_DETERMINISTIC is honoured on the rank steps too)"""
-    from .rasterizer import function as raster_function
-    det = bool(raster_function.DETERMINISTIC_BACKWARD)
-    moments_path = bool(lib.ms_frame_uses_moments(ctypes.byref(desc), int(det)))
+    moments_path, det = frame.backward_mode(desc)
     if moments_path:
-      gr.moments = frame._moments_buffer(device, rows_n, det).data_ptr()
+      self._fixed_exp = frame.attach_moments(gr, g_image, device, rows_n, det)
       gr.boundary_form = _lib.BOUNDARY_COVARIANCE      # the strips hand over dL/d(2D covariance): see include/mi355_splat.h
-      gr.deterministic = int(det)
-      if det:
-        self._fixed_exp = _lib.fixed_point_exponents(g_image)
-        gr.fixed_exp = self._fixed_exp.data_ptr()
     return moments_path, det
 
 
@@ -326,7 +297,7 @@ class StripStep(_RankStep):
       g2d, depths, _ = project_to_image(gaussians, camera_params, self.config)
       o2p, _ = map_to_tiles_strip(g2d, depths, self.image_size, self.config, tile_rows=self.rows,
                                   ndc_range=self.depth_range)
-    self.k_capacity = frame._round_capacity(o2p.shape[0] * slack)
+    self.k_capacity = frame.round_capacity(o2p.shape[0] * slack)
     return self.k_capacity
 
   def step(self, gaussians: Gaussians3D, camera_params: CameraParams, loss_fn: Callable, use_sh: bool = True,
@@ -342,8 +313,8 @@ class StripStep(_RankStep):
     stream = _lib.current_stream(device)
     timer = self.timer
     timer.mark('start')
-    desc, _ = _desc(n, self.image_size, dtype, f, degree, self.config, self.depth_range, tile_rows=self.rows,
-                    capacity=self.k_capacity)
+    desc, _ = frame.frame_desc(n, self.image_size, dtype, f, degree, self.config, self.depth_range, tile_rows=self.rows,
+                               capacity=self.k_capacity)
     inputs = _lib.FrameInputsC(position=pos.data_ptr(), log_scaling=lsc.data_ptr(), rotation=rot.data_ptr(),
                                alpha_logit=alog.data_ptr(), feature=feat.data_ptr(), T_camera_world=Tcw.data_ptr(),
                                projection=proj.data_ptr(), points7=None, depth=None, colours=None)
@@ -357,7 +328,7 @@ class StripStep(_RankStep):
 
     # raster backward of the strip -> (n, 7 + f) 2D-boundary gradients -> sum over the strips
     gr = _lib.FrameGradsC()
-    moments_path, det = self._raster_backward_mode(lib, desc, gr, g_image, device, n)
+    moments_path, det = self._raster_backward_mode(desc, gr, g_image, device, n)
     width = 7 + f
     rows = (n + self.world - 1) // self.world * self.world
     es = image.element_size()
@@ -473,7 +444,7 @@ class ShardedStep(_RankStep):
         distributed.all_reduce_any(biggest, op=dist.ReduceOp.MAX, group=self.group)
       o2p, _ = map_to_tiles_strip(g2, d, self.image_size, self.config, tile_rows=self.rows, ndc_range=self.depth_range)
     self.bucket_capacity = (int(int(biggest.item()) * slack) + 255) // 256 * 256
-    self.k_capacity = frame._round_capacity(o2p.shape[0] * slack)
+    self.k_capacity = frame.round_capacity(o2p.shape[0] * slack)
     return self.bucket_capacity, self.k_capacity
 
   def step(self, shard: Gaussians3D, camera_params: CameraParams, loss_fn: Callable, use_sh: bool = True,
@@ -493,16 +464,16 @@ class ShardedStep(_RankStep):
     timer.mark('start')
 
     # ---- per-gaussian stage on the shard (no compaction: culled gaussians carry depth 0 and are not routed) --------
-    desc_a, _ = _desc(n, self.image_size, dtype, f, degree, self.config, self.depth_range)
-    lay_a = _layout(desc_a)
-    keep_a = _block(lay_a.keep_n_bytes, device)
+    desc_a, _ = frame.frame_desc(n, self.image_size, dtype, f, degree, self.config, self.depth_range)
+    lay_a = frame.frame_layout(desc_a)
+    keep_a = frame.byte_block(lay_a.keep_n_bytes, device)
     in_a = _lib.FrameInputsC(position=pos.data_ptr(), log_scaling=lsc.data_ptr(), rotation=rot.data_ptr(),
                              alpha_logit=alog.data_ptr(), feature=feat.data_ptr(), T_camera_world=Tcw.data_ptr(),
                              projection=proj.data_ptr(), points7=None, depth=None, colours=None)
     _lib.check(lib.ms_frame_project(ctypes.byref(desc_a), ctypes.byref(in_a), keep_a.data_ptr(), stream), "sharded step (project)")
-    points7 = frame._view(keep_a, lay_a.points7, dtype, (n, 7))
-    depth = frame._view(keep_a, lay_a.depth, dtype, (n,))
-    colours = frame._view(keep_a, lay_a.colours, dtype, (n, f)) if degree >= 0 else feat
+    points7 = frame.block_view(keep_a, lay_a.points7, dtype, (n, 7))
+    depth = frame.block_view(keep_a, lay_a.depth, dtype, (n,))
+    colours = frame.block_view(keep_a, lay_a.colours, dtype, (n, f)) if degree >= 0 else feat
     timer.mark('project_sh')
 
     # ---- route into fixed buckets, exchange ------------------------------------------------------------------------
@@ -565,8 +536,8 @@ class ShardedStep(_RankStep):
                  "sharded step (unpack)")
 
     # ---- this rank's strip from the received rows ------------------------------------------------------------------
-    desc_b, _ = _desc(m, self.image_size, dtype, f, -1, self.config, self.depth_range, tile_rows=self.rows,
-                      projected=True, capacity=self.k_capacity)
+    desc_b, _ = frame.frame_desc(m, self.image_size, dtype, f, -1, self.config, self.depth_range, tile_rows=self.rows,
+                                 projected=True, capacity=self.k_capacity)
     in_b = _lib.FrameInputsC(points7=g2.data_ptr(), depth=d2.data_ptr(), colours=f2.data_ptr())
     if colours_ready is not None:
       in_b.colours_ready_event = int(colours_ready.cuda_event)
@@ -585,7 +556,7 @@ class ShardedStep(_RankStep):
 
     # ---- backward: strip raster -> gradients of the received rows -> home -> per-gaussian pass ---------------------
     gr = _lib.FrameGradsC()
-    moments_path, det = self._raster_backward_mode(lib, desc_b, gr, g_image, device, m)
+    moments_path, det = self._raster_backward_mode(desc_b, gr, g_image, device, m)
     row_bytes = self.px_rows[0] * self.image_size[0] * es
     gr.image = image.data_ptr() - row_bytes * f
     g_keep = self._image_grad_pointer(gr, g_image, moments_path, row_bytes * f)      # noqa: F841 (alive until the launch)

@@ -204,7 +204,7 @@ def test_capacity_growth_and_overflow_flag():
   ref = render_gaussians(g, cam, cfg, use_sh=True).image
   frame.USE_FRAME = True
   # a capacity far too small: the eager path notices after the forward is enqueued and re-runs the emission
-  frame._k_capacity[frame._shape_key(torch.device(DEV), 20000, (256, 256), cfg, None, False)] = 1000
+  frame.shape_record(frame._shape_key(torch.device(DEV), 20000, (256, 256), cfg, None, False), create=True).capacity = 1000
   r = render_gaussians(g, cam, cfg, use_sh=True)
   assert torch.equal(r.image, ref)
   st = frame.frame_status(r)

@@ -73,7 +73,7 @@ def test_heavy_tailed_scene_settles_on_the_presort_sequence_with_the_same_image(
       with torch.no_grad():
         images.append(render_gaussians(gd, camd, cfg, use_sh=False).image.clone())
       key = frame._shape_key(torch.device(DEV), n, size, cfg, None, False)
-      modes.append(frame._mapper_mode.get(key))
+      modes.append(getattr(frame.shape_record(key), 'mapper', None))
     from taichi_splatting_amd import _lib
     assert modes[-1] == _lib.MAPPER_PRESORT, modes
     assert torch.equal(images[0], images[1]) and torch.equal(images[1], images[2])
@@ -380,7 +380,7 @@ def test_frame_executor_cuts_long_runs_from_the_second_frame_on():
       if i == 0:
         st = frame.frame_status(r)
         assert st['overlaps'] > 100000
-    assert key in frame._presort_sticky, "no run above 16 384 entries: the scene does not test anything"
+    assert frame.shape_record(key).sticky, "no run above 16 384 entries: the scene does not test anything"
     assert float(out[0][0].max()) > 0.05
     for later in out[1:]:
       assert (later[0] - out[0][0]).abs().max().item() < 3e-6

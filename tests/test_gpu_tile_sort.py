@@ -244,7 +244,7 @@ def test_a_giant_run_moves_the_scene_shape_to_the_presort_sequence():
     # per-tile sort reports the run, the next frame maps with the pre-sort.  (The FIRST frame of an unknown shape maps with
     # the pre-sort anyway since round 6.)
     key = ('2d',) + frame._shape_key(torch.device(DEV), n, size, cfg, None, False)
-    frame._mapper_mode[key] = _lib_direct()
+    frame.shape_record(key, create=True).mapper = _lib_direct()
     modes = []
     for _ in range(3):
       state = frame.FrameState()
@@ -263,7 +263,7 @@ def test_a_giant_run_moves_the_scene_shape_to_the_presort_sequence():
       state.settle()
       torch.cuda.synchronize()
       modes.append((int(state.desc.mapper), int(state.desc.split_long_runs)))
-    assert modes == [(1, 1), (1, 1)] and key in frame._presort_sticky
+    assert modes == [(1, 1), (1, 1)] and frame.shape_record(key).sticky
   finally:
     frame.release_caches()
 

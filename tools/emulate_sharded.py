@@ -410,7 +410,7 @@ def main_static(args):
     st.split_exchange = False
     with torch.no_grad():
       st.step(shard, cam, loss_fn, use_sh=True, backward=False)
-    st.k_capacity = frame._round_capacity(int(st.check()['overlaps']) * 1.15)
+    st.k_capacity = frame.round_capacity(int(st.check()['overlaps']) * 1.15)
     per_rank.append(round(timed(step), 3))
     stages.append(stage_table())
     graph = frame.FrameGraph(step, warmup=1)

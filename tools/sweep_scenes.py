@@ -190,7 +190,7 @@ def measure(spec, dev):
       step()
     torch.cuda.synchronize()
     key = frame._shape_key(dev, g.position.shape[0], size, cfg, None, False)
-    out['frame_mapper'] = {_lib.MAPPER_DIRECT: 'direct', _lib.MAPPER_PRESORT: 'presort'}.get(frame._mapper_mode.get(key), '?')
+    out['frame_mapper'] = {_lib.MAPPER_DIRECT: 'direct', _lib.MAPPER_PRESORT: 'presort'}.get(getattr(frame.shape_record(key), 'mapper', None), '?')
     g.requires_grad_(False)
     frame.release_caches()
   # the mapper's cost is taken from the sequence the frame executor settles on for this scene shape (the modular
@@ -232,7 +232,7 @@ def measure_zoom(dev):
     for _ in range(4):
       r = step(); r.image.sum().backward()
     steady.append(cuda_ms(lambda: step().image.sum().backward(), iters=5, warmup=1))
-    rows.append(dict(K=frame.frame_status(r)['overlaps'], mapper=frame._mapper_mode.get(key)))
+    rows.append(dict(K=frame.frame_status(r)['overlaps'], mapper=getattr(frame.shape_record(key), 'mapper', None)))
   frame.release_caches()
   times, modes = [], []
   for i in range(18):
