@@ -17,20 +17,12 @@
 #include "raster_common.h"
 #include "frame_internal.h"
 
-#ifndef MS_GB_NT
-#define MS_GB_NT 1
-#endif
-
 namespace ms {
 
 // gradient rows are written once and read by somebody else much later (the optimiser): streaming stores
 template <typename V>
 __device__ __forceinline__ void stream_store(V* p, V v) {
-#if MS_GB_NT
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 
 constexpr int GB_MAX_F = 4;      // SH colour channels (sh.hip: SH_MAX_F)

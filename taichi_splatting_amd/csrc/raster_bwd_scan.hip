@@ -41,16 +41,14 @@
 #include "raster_bwd_shared.h"
 #include "frame_internal.h"
 
-// Development builds (tools/abl): -DMS_SCAN_STATS counts chunks / filled lanes / executed pixel steps into
-// g_scan_stats (read with ms_debug_scan_stats); -DMS_SCAN_ABLATE=1 skips the blend phase, =2 the cull + blend.
+// The two instruments (development builds: tools/build_variant.sh).  They measure the product kernel without changing
+// its results.  -DMS_SCAN_STATS=1 counts chunks / filled lanes / executed pixel steps into g_scan_stats (read with
+// ms_debug_scan_stats).
 #ifndef MS_SCAN_STATS
 #define MS_SCAN_STATS 0
 #endif
-#ifndef MS_SCAN_ABLATE
-#define MS_SCAN_ABLATE 0
-#endif
 // -DMS_SCAN_PHASES=1: every wave adds up the shader cycles (s_memtime) it spends in each phase of the kernel
-// (g_scan_phase, read with ms_debug_scan_phases; tools/phase_split.py) — where a wave's wall time goes, parked or not
+// (g_scan_phase_rows, read with ms_debug_scan_phases; tools/rbench.py) — where a wave's wall time goes, parked or not
 #ifndef MS_SCAN_PHASES
 #define MS_SCAN_PHASES 0
 #endif
@@ -63,39 +61,9 @@
 //   commit         point ids of the patch list resolved once per pass (into the dead sub-patch lists), so that a commit
 //                  step is one LDS round trip instead of three dependent ones
 //   cull           both cull levels issue all their LDS reads before the first test
-#ifndef MS_COMMIT_ABLATE
-#define MS_COMMIT_ABLATE 0
-#endif
-// wave priority: 1 = the blend phase runs at raised priority (s_setprio 2), 2 = everything BUT the blend does, 0 = off.
-// Same box, config D: off 1.340-1.345 ms, blend raised 1.334, the rest raised 1.376 — the issue-bound phase should not
-// lose slots to waves that are about to park on a load anyway.
-#ifndef MS_PRIO_MODE
-#define MS_PRIO_MODE 1
-#endif
-#if MS_PRIO_MODE == 1
-#define MS_PRIO_BLEND(on) __builtin_amdgcn_s_setprio((on) ? 2 : 0)
-#elif MS_PRIO_MODE == 2
-#define MS_PRIO_BLEND(on) __builtin_amdgcn_s_setprio((on) ? 0 : 2)
-#else
-#define MS_PRIO_BLEND(on) do {} while (0)
-#endif
-#ifndef MS_GRID_MOMENTS
-#define MS_GRID_MOMENTS 1           // 0: per-pixel moment sums in the splat's frame (rounds 2-3), kept for A/B builds
-#endif
-// tile 32 (one 1024-thread workgroup per tile): staged splats per batch / accumulator rows per wave
-// tile 8 (one wave per tile)
-#ifndef MS_T8_BATCH
-#define MS_T8_BATCH 128
-#endif
-#ifndef MS_T8_CAP
-#define MS_T8_CAP 128
-#endif
-#ifndef MS_T32_BATCH
-#define MS_T32_BATCH 896
-#endif
-#ifndef MS_T32_CAP
-#define MS_T32_CAP 128
-#endif
+// wave priority: the blend phase runs at raised priority (s_setprio 2).  Same box, config D: no priority change
+// 1.340-1.345 ms, blend raised 1.334, everything BUT the blend raised 1.376 — the issue-bound phase should not lose slots
+// to waves that are about to park on a load anyway (the two __builtin_amdgcn_s_setprio calls around the blend).
 
 namespace ms {
 
@@ -157,8 +125,10 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
   // TS == 32 (one 1024-thread workgroup per 32 x 32 tile, 16 waves): an 8x8 patch sees ~1/8 of the tile's splats, so
   // the batch is 896 splats for the per-wave lists to be as long as at tile 16 (~115 patch hits); 43 KB of records +
   // 16 x 6.6 KB per-wave state = 152 of the CU's 160 KB LDS: one workgroup per CU = the same 4 waves per SIMD
-  constexpr int BATCH = TS == 8 ? MS_T8_BATCH : TS == 32 ? MS_T32_BATCH : (TS == 16 && !HEUR) ? 268 : 256;
-  constexpr int BATCH_TARGET = TS == 8 ? MS_T8_BATCH - 16 : TS == 32 ? MS_T32_BATCH - 64 : 256;
+  // tile 8 (one wave per tile) / tile 32 (one 1024-thread workgroup per tile): staged splats per batch
+  constexpr int T8_BATCH = 128, T32_BATCH = 896;
+  constexpr int BATCH = TS == 8 ? T8_BATCH : TS == 32 ? T32_BATCH : (TS == 16 && !HEUR) ? 268 : 256;
+  constexpr int BATCH_TARGET = TS == 8 ? T8_BATCH - 16 : TS == 32 ? T32_BATCH - 64 : 256;
   // Patch hits a wave takes on per pass (>= 64: a pass always advances) = rows of its accumulator.  A wave whose
   // patch list overflows runs the rest of the batch as a second pass with nearly empty chunks, so at tile 16 the
   // 40 KB a workgroup may use (four per CU) go to CAP first and to the staging batch second (config D, ms;
@@ -169,9 +139,9 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
   // visibility (forward.py:127-128) up to the pairs behind a pixel's saturation point, which the backward drops
   // (backward.py:154) and the forward keeps adding: at most 1 - saturate_threshold per pixel.  What the forward sums with
   // a transposing wave reduction per four hits is one addition per pixel step here.  Same LDS: CAP 110 -> 102
-  constexpr int CAP = TS == 16 ? (HEUR ? 102 : 128) : (TS == 32) ? (HEUR ? MS_T32_CAP - 32 : MS_T32_CAP) : (HEUR ? MS_T8_CAP - 12 : MS_T8_CAP);
+  constexpr int T8_CAP = 128, T32_CAP = 128;        // tile 8 / tile 32: accumulator rows per wave (without heuristics)
+  constexpr int CAP = TS == 16 ? (HEUR ? 102 : 128) : (TS == 32) ? (HEUR ? T32_CAP - 32 : T32_CAP) : (HEUR ? T8_CAP - 12 : T8_CAP);
   constexpr int NACC = HEUR ? 12 : 9;
-  constexpr bool GRID_MOMENTS = MS_GRID_MOMENTS != 0;            // see the blend loop
   // largest basis entry (A..D, in units of sqrt(log2 e / 2) / sigma per pixel) a chunk may hold and still use the grid
   // form: 2.5 <=> sigma 0.34 px, where the expansion costs ~3e-5 of the moments' scale (fuzz: tools/fuzz_raster_bwd.py)
   constexpr float GRID_MAX_BASIS = 2.5f;
@@ -187,8 +157,8 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
   // atomics (ds_add_f32 costs ~160 LDS cycles per instruction on gfx950, tools/ubench_scan.hip)
   __shared__ float s_acc[WAVES][CAP][NACC];
   __shared__ uint16_t s_plist[WAVES][CAP];       // patch-list position -> staged index
-  // per sub-patch: patch-list positions of its hits, depth ordered.  (MS_OPT_COMMIT: once a pass has blended, the 4 * CAP
-  // bytes of a wave hold the CAP point ids of its patch list for the commit.)
+  // per sub-patch: patch-list positions of its hits, depth ordered.  (Once a pass has blended, the 4 * CAP bytes of a
+  // wave hold the CAP point ids of its patch list for the commit: commit_pass.)
   __shared__ __attribute__((aligned(16))) uint8_t s_list[WAVES][4][CAP];
   static_assert((4 * CAP) % 4 == 0, "a wave's lists double as CAP ints");
   // per-pixel data, read by ALL lanes of the wave at the pixel's step (same address: LDS broadcast; v_readlane
@@ -202,9 +172,6 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
   const uint64_t ph_start = __builtin_readcyclecounter();
   uint64_t ph_last = ph_start;
   uint32_t ph_acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-#if MS_PRIO_MODE == 2
-  __builtin_amdgcn_s_setprio(2);
 #endif
   int tile_id, quarter = 0, seg_start = 0, seg_end = 0;
   if constexpr (SEGS) {
@@ -385,16 +352,8 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
           __hip_atomic_fetch_add(reinterpret_cast<long long*>(moments) + word,
                                  (long long)llrintf(v * (k == 9 ? fixed_h0 : k == 11 ? VISIBILITY_FIXED_UNIT : fixed_main)),
                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else {
-#if MS_COMMIT_ABLATE == 0
+        else
           atomic_add_noret(moments + word, v);
-#elif MS_COMMIT_ABLATE == 1          // timing experiments (wrong gradients): one lane per row
-          if (k == 0) atomic_add_noret(moments + word, v);
-#elif MS_COMMIT_ABLATE == 2          // plain stores to the same addresses
-          moments[word] = v;
-#elif MS_COMMIT_ABLATE == 3          // no global traffic at all
-#endif
-        }
         s_acc[wave][e][k] = 0.0f;
       }
       v = vn; point = pointn;
@@ -466,9 +425,6 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
     // wave-wide early out (backward.py:142): a wave whose 64 pixels are saturated skips the passes — but not the batch's
     // stage point below (one site for every path)
     wave_alive = __ballot(__float_as_uint(s_pix[wave][lane].w) > oms_bits) != 0;
-#if MS_SCAN_ABLATE == 2
-    wave_alive = false;
-#endif
 
 #if MS_SCAN_STATS
     // balance of the blend work between the waves of a workgroup: per batch, sum and WAVES x max of the chunks
@@ -548,8 +504,7 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
 #endif
 
       // ---- blend: lane = splat, 16 pixel steps per chunk ------------------------------------------------------
-#if MS_SCAN_ABLATE != 1
-      MS_PRIO_BLEND(true);
+      __builtin_amdgcn_s_setprio(2);         // (wave priority: see the top of the file)
 #pragma unroll 1
       for (int q = 0; q < 4; ++q) {
         const int n = q == 0 ? cnt[0] : q == 1 ? cnt[1] : q == 2 ? cnt[2] : cnt[3];
@@ -578,7 +533,7 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
 
           float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f, m5 = 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f;
           float h0 = 0.f, h1 = 0.f, vs = 0.f;
-          // GRID_MOMENTS: the six moments are first taken in the sub-patch's own pixel grid,
+          // Grid form: the six moments are first taken in the sub-patch's own pixel grid,
           //   n = sum q {1, x, y, x^2, x y, y^2},  x, y in 0..3,
           // where x and y are compile-time constants of the unrolled steps: a pixel row keeps r = sum_x q {1, x, x^2}
           // (7 additions / FMAs for its four pixels), a row end folds r into n with the constants y, y^2 (3 to 6), and
@@ -744,13 +699,8 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
           };
           {
             const bool steep = fmaxf(fmaxf(fabsf(A), fabsf(B)), fmaxf(fabsf(C), fabsf(D))) > GRID_MAX_BASIS;
-#if MS_GRID_MOMENTS == 2               // A/B builds: the grid form whatever the basis
-            (void)steep;
-            blend_chunk(std::true_type{});
-#else
-            if (GRID_MOMENTS && __ballot(valid && steep) == 0) blend_chunk(std::true_type{});
+            if (__ballot(valid && steep) == 0) blend_chunk(std::true_type{});
             else blend_chunk(std::false_type{});
-#endif
           }
 #if MS_SCAN_STATS
           ++batch_chunks;
@@ -776,8 +726,7 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
         }
       }
 
-      MS_PRIO_BLEND(false);
-#endif      // MS_SCAN_ABLATE != 1
+      __builtin_amdgcn_s_setprio(0);
       wave_lds_fence();
       MS_PH(4);        // (the sub-patch loop's own bookkeeping between the last chunk and the commit)
       if (r >= count) break;       // last pass of the batch: committed below, behind the stage point
@@ -957,13 +906,6 @@ static int launch_scan_backward(const float* points7, const float* features,
   // the splat-row table serves the one-workgroup-per-tile kernels of tile 16 and 32 (tile 8 gathers inside its pass
   // loop and measured 10 % SLOWER with the 16-byte loads; the quarter-tile variant is a fallback)
   const bool hf = cfg->compute_point_heuristic;
-#ifdef MS_WITH_ROWS_KERNEL      // tools/experiments/raster_bwd_rows.hip (measured and dropped in round 4)
-  if (launch_rows_backward(points7, features, tile_ranges, overlap_to_point, image, grad_image, rp, ts, hf, moments,
-                           fixed_exp, s)) {
-    MS_CHECK_LAUNCH();
-    return 0;
-  }
-#endif
   const hipEvent_t probe_start = g_probe_start, probe_stop = g_probe_stop;
   g_probe_start = g_probe_stop = nullptr;                      // one launch per arming
   if (probe_start) (void)hipEventRecord(probe_start, s);

@@ -1,6 +1,5 @@
-// raster_bwd_shared.h — building blocks of the splat-per-lane raster backward (raster_bwd_scan.hip; also included by the
-// measured-and-dropped round-4 variant tools/experiments/raster_bwd_rows.hip): the wave-wide DPP prefix scans, the
-// 48-byte LDS record of a staged splat and the conservative rectangle test.
+// raster_bwd_shared.h — building blocks of the splat-per-lane raster backward (raster_bwd_scan.hip): the wave-wide DPP
+// prefix scans, the 48-byte LDS record of a staged splat and the conservative rectangle test.
 #pragma once
 #include "raster_common.h"
 

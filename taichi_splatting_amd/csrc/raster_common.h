@@ -148,15 +148,6 @@ __device__ __forceinline__ Raw load_raw(const float* __restrict__ points, const 
 // The hardware forms are within 1 ulp: v_rcp_f32 with one Newton step for the basis (0.5-1 ulp, the basis enters
 // every alpha), plain v_rcp_f32 / v_sqrt_f32 / v_log_f32 for the cull data, whose margins (x 1.001, + 0.01 px,
 // x 1.002) are four orders of magnitude wider.
-#ifndef MS_SLOW_STAGING
-#define MS_SLOW_STAGING 0            // 1: the library forms (A/B builds, tools/build_variant.sh)
-#endif
-#if MS_SLOW_STAGING
-__device__ __forceinline__ float rcp_newton(float x) { return 1.0f / x; }
-__device__ __forceinline__ float stage_rcp(float x) { return 1.0f / x; }
-__device__ __forceinline__ float fast_sqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ float fast_log2(float x) { return log2f(x); }
-#else
 __device__ __forceinline__ float rcp_newton(float x) {
   const float r = __builtin_amdgcn_rcpf(x);
   const float e = __builtin_fmaf(-x, r, 1.0f);          // NaN for x = 0 / inf (r = inf / 0): the step is skipped
@@ -165,7 +156,6 @@ __device__ __forceinline__ float rcp_newton(float x) {
 __device__ __forceinline__ float stage_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }
-#endif
 // cutoff radius of the contribution region alpha g > threshold in units of sigma: sqrt(2 ln(alpha / threshold)),
 // NaN when alpha < threshold (every comparison of the hit tests then fails: culled)
 __device__ __forceinline__ float cutoff_radius(float alpha, float alpha_threshold) {
@@ -290,7 +280,10 @@ __device__ __forceinline__ float wave_reduce4(const float (&v)[4], bool b0, bool
 }
 
 // v_min_f32 without the canonicalising v_max hipcc puts in front of fminf (inputs are never sNaN here).
-// NOT directly after the transcendental instruction that produces an operand: see clamp_alpha().
+// NOT directly after the transcendental instruction that produces an operand: gfx950 needs a wait state between a
+// transcendental result and its VALU use, the hazard recogniser does not look into inline assembly, and half of the
+// lanes then read the stale register (seen in the forward's hit loop once nothing else was scheduled in between; the
+// forward now clamps with the compiler-visible v_med3_f32 of fwd_alpha, raster_fast.hip).
 __device__ __forceinline__ float min_f32(float a, float b) {
   float r;
   asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -304,14 +297,6 @@ __device__ __forceinline__ float min_f32_uniform(float a, float uniform_b) {
   float r;
   asm("v_min_f32 %0, %2, %1" : "=v"(r) : "v"(a), "s"(uniform_b));
   return r;
-}
-
-// min(e, clamp) for e >= 0 as ONE compiler-visible instruction (v_med3_f32 e, 0, clamp).  The inline-assembly
-// v_min_f32 above must not directly follow the v_exp_f32 that produces its operand: gfx950 needs a wait state between
-// a transcendental result and its VALU use, the hazard recogniser does not look into inline assembly, and half of the
-// lanes then read the stale register (seen in the forward's hit loop once nothing else was scheduled in between).
-__device__ __forceinline__ float clamp_alpha(float e, float clamp_max_alpha) {
-  return __builtin_amdgcn_fmed3f(e, 0.0f, clamp_max_alpha);
 }
 
 // Lanes of one wave hand data to each other through LDS (hit lists, accumulator rows).  LDS operations of a wave

@@ -16,27 +16,11 @@
 //     current batch is consumed, hiding the dependent HBM/L2 gather latency behind the blend loop.
 #include "raster_common.h"
 
-#ifndef MS_ABLATE
-#define MS_ABLATE 0
-#endif
-// Forward variants (round 6, tools/build_variant.sh; profiles/r06_raster_fwd_phase_split.txt):
+// The instrument (a development build: tools/build_variant.sh; profiles/r06_raster_fwd_phase_split.txt).  It measures
+// the product kernel without changing its results.
 //   MS_FWD_PHASES      every wave adds up the shader cycles it spends per phase (ms_debug_fwd_phases, tools/rbench.py)
-//   MS_FWD_CLAMP_FOLD  the clamp of alpha to clamp_max_alpha as the free `clamp` output modifier of v_exp_f32: the
-//                      exponent carries + log2(clamp_max), the pixel state is T' = clamp_max T (w = a' T', T' -= clamp_max w)
-//   MS_FWD_SKIP_EMPTY  a hit none of whose 64 pixels passes the blend gate (the cull is conservative) leaves before
-//                      the colour read and the blend arithmetic
 #ifndef MS_FWD_PHASES
 #define MS_FWD_PHASES 0
-#endif
-#ifndef MS_FWD_CLAMP_FOLD
-#define MS_FWD_CLAMP_FOLD 1
-#endif
-#ifndef MS_FWD_SKIP_EMPTY
-#define MS_FWD_SKIP_EMPTY 0
-#endif
-//   MS_FWD_PAIR        the hit walk takes two hits per iteration (both records requested before either is used)
-#ifndef MS_FWD_PAIR
-#define MS_FWD_PAIR 1
 #endif
 // Hit-loop flavour (both measured on config D): the forward walks the hit mask with the record of the next hit
 // requested one iteration ahead; the backward body is long enough for the other waves of the SIMD to hide the
@@ -64,14 +48,11 @@ constexpr float FWD_SPENT_T = 1.3552527e-20f;   // 2^-66: transmittance below wh
 constexpr unsigned FWD_XCD_CHUNK = 8;      // tiles per XCD run (xcd_tile, raster_common.h)
 constexpr unsigned BWD_XCD_CHUNK = 8;      // pixel-per-lane backward: 3.12 -> 3.08 ms at tile 32, 2.84 -> 2.79 at tile 16
 
-#if MS_FWD_CLAMP_FOLD
-// exp2 of the biased exponent = alpha g / clamp_max; clamp(., 0, 1) is the v_exp_f32's own output modifier (no v_med3)
+// The clamp of alpha to clamp_max_alpha is folded into the exponential (round 6): the exponent carries + log2(clamp_max)
+// (FWD_ALPHA_BIAS), so exp2 of it = alpha g / clamp_max, and clamp(., 0, 1) is the v_exp_f32's own output modifier (no
+// v_med3).  The pixel state is T' = clamp_max T (w = a' T', T' -= clamp_max w).
 #define FWD_ALPHA_BIAS (__builtin_amdgcn_logf(rp.clamp_max_alpha))
-__device__ __forceinline__ float fwd_alpha(float e, float) { return __builtin_amdgcn_fmed3f(e, 0.0f, 1.0f); }
-#else
-#define FWD_ALPHA_BIAS 0.0f
-__device__ __forceinline__ float fwd_alpha(float e, float clamp_max_alpha) { return clamp_alpha(e, clamp_max_alpha); }
-#endif
+__device__ __forceinline__ float fwd_alpha(float e) { return __builtin_amdgcn_fmed3f(e, 0.0f, 1.0f); }
 
 template <int TS, bool VIS, bool ROWS, bool SEGS = false>   // ROWS: `points` is a splat-row table (common.h), `feats` unused;
 __global__ void __launch_bounds__(TS * TS)                  // SEGS: one workgroup per SEGMENT of a long tile run (raster_common.h)
@@ -122,12 +103,8 @@ raster_fwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
   const float pxr = px - origin_x, pyr = py - origin_y;
 
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  // transmittance = 1 - accumulated weight, carried as T' = TSCALE T (MS_FWD_CLAMP_FOLD: TSCALE = clamp_max_alpha)
-#if MS_FWD_CLAMP_FOLD
+  // transmittance = 1 - accumulated weight, carried as T' = TSCALE T (TSCALE = clamp_max_alpha: see fwd_alpha)
   const float TSCALE = rp.clamp_max_alpha, GATE = rp.alpha_threshold / rp.clamp_max_alpha;
-#else
-  const float TSCALE = 1.0f, GATE = rp.alpha_threshold;
-#endif
   float T = in_bounds ? TSCALE : 0.0f;
   // SEGS + VIS = the SECOND walk of a segment, behind the composition pass: it starts from the true transmittance at
   // the segment's start (what the composition left in the state) and exists for the visibility sums only
@@ -212,7 +189,7 @@ raster_fwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
               const float2 q2 = *reinterpret_cast<const float2*>(&s_rec[(r + b) * 3 + 2]);
               const float X = __builtin_fmaf(pxr, q0.z, __builtin_fmaf(pyr, q0.w, -q0.x));
               const float Y = __builtin_fmaf(pxr, q1.x, __builtin_fmaf(pyr, q1.y, -q0.y));
-              const float a = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y, Y, __builtin_fmaf(X, X, q1.z))), rp.clamp_max_alpha);
+              const float a = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y, Y, __builtin_fmaf(X, X, q1.z))));
               const float w = a > GATE ? a * T : 0.0f;
               T = __builtin_fmaf(-TSCALE, w, T);
               c0 += q1.w * w; c1 += q2.x * w; c2 += q2.y * w;
@@ -232,7 +209,6 @@ raster_fwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
       // a time — a wave alone needs ~190 cycles per hit (LDS round trip, then fourteen dependent VALU instructions)
       // while its share of the SIMD's issue slots is ~40: with both records requested up front and the two alpha chains
       // independent until the transmittance, the scheduler interleaves them (profiles/r06_raster_fwd_phase_split.txt)
-#if MS_FWD_PAIR
       while (m & (m - 1)) {                                // at least two hits left
         const int b0 = __builtin_ctzll(m);
         asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(b0));
@@ -246,8 +222,8 @@ raster_fwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
         const float X1 = __builtin_fmaf(pxr, q0.z, __builtin_fmaf(pyr, q0.w, -q0.x));
         const float Y0 = __builtin_fmaf(pxr, p1.x, __builtin_fmaf(pyr, p1.y, -p0.y));
         const float Y1 = __builtin_fmaf(pxr, q1.x, __builtin_fmaf(pyr, q1.y, -q0.y));
-        const float a0 = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y0, Y0, __builtin_fmaf(X0, X0, p1.z))), rp.clamp_max_alpha);
-        const float a1 = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y1, Y1, __builtin_fmaf(X1, X1, q1.z))), rp.clamp_max_alpha);
+        const float a0 = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y0, Y0, __builtin_fmaf(X0, X0, p1.z))));
+        const float a1 = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y1, Y1, __builtin_fmaf(X1, X1, q1.z))));
         const float w0 = a0 > GATE ? a0 * T : 0.0f;
         T = __builtin_fmaf(-TSCALE, w0, T);
         c0 += p1.w * w0; c1 += p2.x * w0; c2 += p2.y * w0;
@@ -255,27 +231,22 @@ raster_fwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
         T = __builtin_fmaf(-TSCALE, w1, T);
         c0 += q1.w * w1; c1 += q2.x * w1; c2 += q2.y * w1;
       }
-#endif
       while (m != 0) {
         const int b = __builtin_ctzll(m);
         asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(b));
         // the forward uses 40 of the record's 48 bytes: the third read is 64 bits
         const float4 q0 = s_rec[(r + b) * 3 + 0], q1 = s_rec[(r + b) * 3 + 1];
-#if !MS_FWD_SKIP_EMPTY
         const float2 q2 = *reinterpret_cast<const float2*>(&s_rec[(r + b) * 3 + 2]);
-#endif
         // (X, Y) = basis * (pixel - mean), expanded around the tile centre (write_records<true>)
         const float X = __builtin_fmaf(pxr, q0.z, __builtin_fmaf(pyr, q0.w, -q0.x));
         const float Y = __builtin_fmaf(pxr, q1.x, __builtin_fmaf(pyr, q1.y, -q0.y));
         // alpha * g in one exponential: A..D pre-scaled, q1.z = -log2(alpha) [+ log2(clamp_max)] (write_records<true>)
-        const float a = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y, Y, __builtin_fmaf(X, X, q1.z))), rp.clamp_max_alpha);
+        const float a = fwd_alpha(__builtin_amdgcn_exp2f(-__builtin_fmaf(Y, Y, __builtin_fmaf(X, X, q1.z))));
         // (the gate as arithmetic — clamp((E0 - e) 2^40, 0, 1) folded into an FMA, then a multiply — was measured in
         // round 4: 0.545 -> 0.560 ms on the same box; the compare + select stays)
+        // (leaving a hit none of whose 64 pixels passes the gate before the colour read and the blend arithmetic — the
+        // cull is conservative — was measured in round 6: +26 %)
         const bool pass = a > GATE;
-#if MS_FWD_SKIP_EMPTY
-        if (__ballot(pass) == 0) continue;
-        const float2 q2 = *reinterpret_cast<const float2*>(&s_rec[(r + b) * 3 + 2]);
-#endif
         const float w = pass ? a * T : 0.0f;
         T = __builtin_fmaf(-TSCALE, w, T);
         c0 += q1.w * w; c1 += q2.x * w; c2 += q2.y * w;
@@ -290,9 +261,7 @@ raster_fwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
     if (stager && s_vis[t] != 0.0f) atomic_add_noret(visibility + s_id[t], s_vis[t]);
   }
 
-#if MS_FWD_CLAMP_FOLD
   T = T / TSCALE;                          // back to the transmittance itself (correctly rounded division, once per pixel)
-#endif
 #if MS_FWD_PHASES
   if (g_fwd_phase_rows && lane == 0) {
     unsigned long long* row = g_fwd_phase_rows + ((size_t)blockIdx.x * (TS * TS / 64) + wave) * 12;
@@ -510,18 +479,8 @@ raster_bwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
           }
           v[12] = 0.f; v[13] = 0.f; v[14] = 0.f; v[15] = 0.f;
 
-#if MS_ABLATE == 1   /* profiling only: no cross-lane reduction */
-          const float total = v[0] + v[1] + v[2] + v[3] + v[4] + v[5] + v[6] + v[7] + v[8] + v[9];
-#else
           const float total = wave_reduce16(v, b0, b1);
-#endif
-#if MS_ABLATE == 2   /* profiling only: no atomic commit */
-          if (tgt && total == 123.456f) {
-#else
-          if (tgt) {
-#endif
-            atomic_add_noret(tgt + (size_t)tgt_off[r + b], total);
-          }
+          if (tgt) atomic_add_noret(tgt + (size_t)tgt_off[r + b], total);
         }
 
       }

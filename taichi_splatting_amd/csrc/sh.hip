@@ -7,10 +7,6 @@
 #include "common.h"
 #include "frame_internal.h"
 
-#ifndef MS_SH_ROWS_BLOCKS
-#define MS_SH_ROWS_BLOCKS 16384
-#endif
-
 namespace ms {
 
 constexpr int SH_MAX_F = 4;
@@ -338,7 +334,8 @@ int sh_fwd_inplace_launch(const void* params, const void* positions, const void*
   static const bool rows_off = [] { const char* e = getenv("MS_SH_FWD"); return e && e[0] == 'w'; }();   // "walk": the per-lane row walk
   if (dtype == MS_F32 && f == 3 && degree == 3 && !rows_off && (reinterpret_cast<uintptr_t>(params) & 15) == 0) {
     int64_t blocks = div_up(n, 256);
-    if (blocks > MS_SH_ROWS_BLOCKS) blocks = MS_SH_ROWS_BLOCKS;       // grid-stride: a resident grid streams best
+    constexpr int64_t ROWS_BLOCKS = 16384;
+    if (blocks > ROWS_BLOCKS) blocks = ROWS_BLOCKS;       // grid-stride: a resident grid streams best
     if (splat_rows)
       sh_fwd_rows_deg3_kernel<true><<<dim3((unsigned)blocks), dim3(256), 0, s>>>((const float*)params, (const float*)positions,
                                                                                 (const float*)cam_pos, (const float*)depth, n,

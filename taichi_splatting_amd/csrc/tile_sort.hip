@@ -23,15 +23,7 @@ constexpr int TS_THREADS = 256;
 constexpr int TS_WAVES = TS_THREADS / 64;
 constexpr int TS_COST_LIMIT = 64;          // bucket path: at most this many comparisons per entry on average
 // run-length classes: 256 * R entries held in LDS by one workgroup (tuned on the bench scene)
-#ifndef TS_SMALL_R
-#define TS_SMALL_R 4
-#endif
-#ifndef TS_MID_R
-#define TS_MID_R 10                         // 0: no middle class
-#endif
-#ifndef TS_LONG_R
-#define TS_LONG_R 20
-#endif
+constexpr int SMALL_R = 4, MID_R = 10, LONG_R = 20;
 
 constexpr int TS_PER_WAVE = 256;           // bounded path: entries a wave ranks per round of the workgroup
 struct TsShared {
@@ -361,17 +353,13 @@ void tile_depth_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uint6
                             uint64_t* scratch, hipStream_t s, int32_t* run_stats, int32_t* run_host) {
   if (num_tiles <= 0) return;
   const dim3 per_tile((unsigned)num_tiles), block(TS_THREADS);
-  int covered = TS_THREADS * TS_SMALL_R;
-  tile_depth_sort_kernel<TS_SMALL_R><<<per_tile, block, 0, s>>>(tile_ranges, sorted_keys, overlap_to_point, scratch, 1, covered,
-                                                                run_stats);
-#if TS_MID_R > 0
-  tile_depth_sort_kernel<TS_MID_R><<<per_tile, block, 0, s>>>(tile_ranges, sorted_keys, overlap_to_point, scratch, covered,
-                                                             TS_THREADS * TS_MID_R, run_stats);
-  covered = TS_THREADS * TS_MID_R;
-#endif
+  tile_depth_sort_kernel<SMALL_R><<<per_tile, block, 0, s>>>(tile_ranges, sorted_keys, overlap_to_point, scratch, 1,
+                                                            TS_THREADS * SMALL_R, run_stats);
+  tile_depth_sort_kernel<MID_R><<<per_tile, block, 0, s>>>(tile_ranges, sorted_keys, overlap_to_point, scratch,
+                                                          TS_THREADS * SMALL_R, TS_THREADS * MID_R, run_stats);
   const int64_t few = 2 * 256;             // two workgroups of the long-run kernel fit a CU
-  tile_depth_sort_long_kernel<TS_LONG_R><<<dim3((unsigned)(num_tiles < few ? num_tiles : few)), block, 0, s>>>(
-      tile_ranges, num_tiles, sorted_keys, overlap_to_point, scratch, covered, run_stats, run_host);
+  tile_depth_sort_long_kernel<LONG_R><<<dim3((unsigned)(num_tiles < few ? num_tiles : few)), block, 0, s>>>(
+      tile_ranges, num_tiles, sorted_keys, overlap_to_point, scratch, TS_THREADS * MID_R, run_stats, run_host);
 }
 
 }  // namespace ms

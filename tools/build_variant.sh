@@ -1,24 +1,25 @@
 #!/bin/bash
-# Build a development variant of libmi355_splat.so into tools/variants/lib<name>.so with extra hipcc flags:
-#   tools/build_variant.sh stats -DMS_SCAN_STATS=1
+# Build an instrumented development variant of libmi355_splat.so into tools/variants/lib<name>.so: the product sources
+# and flags (SRCS and CXXFLAGS of taichi_splatting_amd/csrc/Makefile) plus the extra hipcc flags given here.  The three
+# instruments measure the product kernels without changing their results, and are the only supported variants:
+#   tools/build_variant.sh stats     -DMS_SCAN_STATS=1     (ms_debug_scan_stats:  work counters of the raster backward)
+#   tools/build_variant.sh phases    -DMS_SCAN_PHASES=1    (ms_debug_scan_phases: a backward wave's cycles per phase)
+#   tools/build_variant.sh fwdphases -DMS_FWD_PHASES=1     (ms_debug_fwd_phases:  a forward wave's cycles per phase)
 # Select it at run time with MS_SPLAT_LIB=tools/variants/lib<name>.so (taichi_splatting_amd/_lib.py).
 set -e
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)
 src=$root/taichi_splatting_amd/csrc
 out=$root/tools/variants/obj_$name
+makevar() { make -s -C "$src" --no-print-directory --eval='print-%: ; @echo $($*)' "print-$1"; }
+hipcc=$(makevar HIPCC); flags=$(makevar CXXFLAGS); srcs=$(makevar SRCS)
 mkdir -p "$out"
-flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -fno-fast-math -fno-slp-vectorize"
 pids=()
-for f in lib projection sh mapper scan_sort tile_sort raster raster_fast raster_bwd_scan strip_route morton optim gaussian_bwd frame; do
-  /opt/rocm/bin/hipcc $flags "$@" -c "$src/$f.hip" -o "$out/$f.o" &
+for f in $srcs; do
+  $hipcc $flags "$@" -c "$src/$f" -o "$out/${f%.hip}.o" &
   pids+=($!)
 done
-case " $* " in *MS_WITH_ROWS_KERNEL*)      # the round-4 experiment, tools/experiments/raster_bwd_rows.hip
-  /opt/rocm/bin/hipcc $flags "$@" -I"$src" -c "$root/tools/experiments/raster_bwd_rows.hip" -o "$out/raster_bwd_rows.o" &
-  pids+=($!);;
-esac
 for p in "${pids[@]}"; do wait "$p"; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/tools/variants/lib$name.so" "$out"/*.o
+$hipcc --offload-arch=$(makevar ARCH) -shared -fPIC -o "$root/tools/variants/lib$name.so" "$out"/*.o
 rm -rf "$out"
 echo "built tools/variants/lib$name.so"

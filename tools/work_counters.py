@@ -5,7 +5,6 @@ statement in bench.py's `roofline.compute`.  Condenses
 
   * the -DMS_SCAN_STATS build   (sub-patch hits, chunks, fill, executed pixel steps, CONTRIBUTING (pixel, splat) pairs),
   * the -DMS_SCAN_PHASES build  (share of a wave's cycles per phase),
-  * the ablation builds         (-DMS_SCAN_ABLATE=2: staging only; =1: no blend; -DMS_COMMIT_ABLATE=3: no commit traffic),
   * the product build,
 
 and the table of tools/ubench_blend.bin (the blend phase alone, 1..8 waves per SIMD):
@@ -38,13 +37,8 @@ if phases:
   out['wave_cycle_share'] = phases['phases_frac']
   out['cycles_per_chunk'] = phases['cycles_per_chunk']
   out['phases_build_ms'] = phases['bwd_ms_mean_med_min'][1]
-alone = {}
-for key, name in (('product', 'product'), ('staging_only', 'abl2'), ('no_blend', 'abl1'), ('no_commit_traffic', 'commit3'),
-                  ('commit_plain_stores', 'commit2'), ('commit_one_lane_per_row', 'commit1')):
-  r = rbench(name)
-  if r:
-    alone[key + '_ms'] = r['bwd_ms_mean_med_min'][1]
-out['kernel_ms_same_box'] = alone
+if prod:
+  out['kernel_ms_same_box'] = {'product_ms': prod['bwd_ms_mean_med_min'][1]}
 ub = d / 'ubench_blend.txt'
 if ub.exists():
   table = {}
