@@ -557,6 +557,24 @@ int ms_optim_visibility_weights(const int64_t* indexes, const float* visibility,
 int ms_morton_codes64(const float* points3, int64_t n, const float* lower3_host, const float* inc3_host,
                       uint32_t size, uint64_t* out_codes, void* stream);
 
+/* ---- k nearest neighbours of a 3-D point set (no reference counterpart; upstream trainers use simple_knn) ----
+ * Exact: out_dist2 (N, k) float32 = the k smallest squared distances from points3[i] (N, 3 float32) to the OTHER points
+ * of the same array, ascending; out_index (N, k) = their indices.  Self is excluded by index, so a duplicate point is a
+ * neighbour at distance 0; a missing neighbour (N - 1 < k) is +inf / -1.  1 <= k <= 8, N < 2^31.
+ * d2 = (dx dx + dy dy) + dz dz on float32 differences, unfused: out_dist2 is bitwise independent of `order`.
+ * order: a permutation of 0..N-1 (device), normally the argsort of ms_morton_codes64 by ms_radix_sort_pairs: consecutive
+ * runs of MS_KNN_BLOCK points in that order are the blocks whose boxes prune the search.  The results do not depend on
+ * which permutation, only the speed does (an entry outside 0..N-1 is clamped: wrong results, no stray access).
+ * out_stats: NULL, or a device int64[2] to which the search ADDS [blocks scanned x queries of the wave, point-query
+ * distance evaluations] (the caller zeroes it); brute force would evaluate N (N - 1).
+ * tmp: call with tmp == NULL for *tmp_bytes.  No host read, allocation or synchronisation: capturable into a graph.
+ * MS_ERR_BAD_ARG names the argument: n < 0, n >= 2^31, k, null points3 / order / out_dist2 with n > 0, null tmp_bytes,
+ * *tmp_bytes too small.  n == 0 returns 0 without a launch. */
+#define MS_KNN_BLOCK 256
+int ms_knn_points(const float* points3, const int32_t* order, int64_t n, int k,
+                  float* out_dist2, int32_t* out_index /* may be NULL */, int64_t* out_stats /* may be NULL */,
+                  void* tmp, size_t* tmp_bytes, void* stream);
+
 /* ---- camera position ----------------------------------------------------------------------------------
  * out_position3 = inverse(T_camera_world)[0:3, 3] for a row-major 4x4 (perspective/params.py:62-65), one
  * launch instead of a device-side LU. */

@@ -41,7 +41,7 @@ def install_as_taichi_splatting():
   for sub in ('data_types', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
-              'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'optim', 'optim.fractional',
+              'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'optim', 'optim.fractional',
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',

@@ -27,6 +27,7 @@ ABI_VERSION = 500  # MS_VERSION of include/mi355_splat.h this binding was writte
 PAD_SAME, PAD_VALID = 0, 1                         # MS_PAD_SAME / MS_PAD_VALID (ms_photometric_*)
 MOMENT_ROW = 16   # MS_MOMENT_ROW of include/mi355_splat.h
 SPLAT_ROW = 16    # MS_SPLAT_ROW
+KNN_BLOCK = 256   # MS_KNN_BLOCK: sorted points per block of ms_knn_points
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -148,6 +149,7 @@ SIGNATURES = {
   'ms_tile_depth_sort': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
   'ms_fractional_step': (c_int, [c_int, c_int] + [c_void_p] * 7 + [c_int64, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p]),
   'ms_morton_codes64': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p]),
+  'ms_knn_points': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
   'ms_camera_position': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
   'ms_strip_route_blocks': (c_int, [c_int]),
   'ms_strip_route_count': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 import math
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -54,6 +54,9 @@ class RasterConfig:
     # reference rasterizer/backward.py:32-33
     assert (self.tile_size * self.tile_size) // (sx * sy) >= 32, \
       f"pixel_stride {self.pixel_stride} and tile_size {self.tile_size} must allow at least one warp sized (32) tile"
+
+
+SH_C0 = 0.28209479177387814    # Y_0^0: colour = 0.5 + SH_C0 * coefficient 0 for a degree-0 feature
 
 
 def check_packed3d(packed_gaussians: torch.Tensor):
@@ -137,6 +140,52 @@ class Gaussians3D(TensorClass):
   @staticmethod
   def concat_batch(gaussians: List['Gaussians3D']) -> 'Gaussians3D':
     return Gaussians3D.cat(gaussians, dim=0)
+
+  @staticmethod
+  def from_point_cloud(points: torch.Tensor, colours: Optional[torch.Tensor] = None, *, sh_degree: Optional[int] = None,
+                       k: int = 3, initial_alpha: float = 0.1, min_dist2: float = 1e-7) -> 'Gaussians3D':
+    """Initial gaussians of a sparse point cloud, as the upstream trainers build them (no reference counterpart):
+    isotropic, scale = sqrt of the mean squared distance to the k nearest other points (``misc.knn.mean_knn_dist2``,
+    clamped below by ``min_dist2``), identity rotation (xyzw), alpha = ``initial_alpha``.
+
+    ``colours`` (N, 3) in [0, 1], 0.5 when omitted.  ``sh_degree=None``: feature = colours, (N, 3).  ``sh_degree=D``:
+    feature (N, 3, (D + 1)^2) with coefficient 0 = (colours - 0.5) / SH_C0 and the rest zero, the layout
+    ``evaluate_sh_at`` and ``render_gaussians(use_sh=True)`` read.  The points must be on the GPU (the neighbour search
+    has no CPU fallback) and N >= 2; like ``misc.knn.knn`` this reads the points' bounding box back to the host once.
+    """
+    if not isinstance(points, torch.Tensor) or points.ndim != 2 or points.shape[1] != 3:
+      raise ValueError(f"points must be a (N, 3) tensor, got {tuple(getattr(points, 'shape', ()))}")
+    n = points.shape[0]
+    if n < 2:
+      raise ValueError(f"from_point_cloud needs at least 2 points, got {n}")
+    if colours is not None and (not isinstance(colours, torch.Tensor) or colours.shape != (n, 3)):
+      raise ValueError(f"colours must be a ({n}, 3) tensor, got {tuple(getattr(colours, 'shape', ()))}")
+    if colours is not None and colours.device != points.device:
+      raise ValueError(f"colours are on {colours.device}, points on {points.device}")
+    if sh_degree is not None and (not isinstance(sh_degree, int) or isinstance(sh_degree, bool) or not 0 <= sh_degree <= 3):
+      raise ValueError(f"sh_degree must be None or an integer in 0..3 (the SH kernels' range), got {sh_degree!r}")
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= 8:
+      raise ValueError(f"k must be an integer in 1..8, got {k!r}")
+    if not 0.0 < initial_alpha < 1.0:
+      raise ValueError(f"initial_alpha must be inside (0, 1), got {initial_alpha}")
+    if not min_dist2 > 0.0:
+      raise ValueError(f"min_dist2 must be positive, got {min_dist2}")
+
+    from .misc.knn import mean_knn_dist2     # (imports the kernel library: kept out of the data model's import)
+    position = points.detach().to(torch.float32).contiguous()
+    dist2 = mean_knn_dist2(position, k)
+    log_scale = torch.log(torch.sqrt(torch.clamp_min(dist2, min_dist2)))
+    rotation = position.new_zeros((n, 4))
+    rotation[:, 3] = 1.0
+    alpha_logit = inverse_sigmoid(position.new_full((n, 1), float(initial_alpha)))
+    rgb = position.new_full((n, 3), 0.5) if colours is None else colours.detach().to(torch.float32)
+    if sh_degree is None:
+      feature = rgb.clone()
+    else:
+      feature = position.new_zeros((n, 3, (sh_degree + 1) ** 2))
+      feature[:, :, 0] = (rgb - 0.5) / SH_C0
+    return Gaussians3D(position=position, log_scaling=log_scale.unsqueeze(1).repeat(1, 3), rotation=rotation,
+                       alpha_logit=alpha_logit, feature=feature, batch_size=(n,))
 
 
 def inverse_sigmoid(x: torch.Tensor):
