@@ -18,6 +18,7 @@ from . import optim
 from .perspective import CameraParams
 from .taichi_queue import TaichiQueue, taichi_queue, queued
 from .loss import l1_ssim_loss, ssim
+from .scene_io import load_ply, save_ply, read_ply_header
 
 __version__ = '0.5.0'       # = MS_VERSION 500 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -29,6 +30,7 @@ __all__ = [
   'rasterize', 'rasterize_with_tiles',
   'perspective', 'TaichiQueue',
   'l1_ssim_loss', 'ssim',
+  'load_ply', 'save_ply', 'read_ply_header',
 ]
 
 
@@ -38,7 +40,7 @@ def install_as_taichi_splatting():
   import sys
   me = sys.modules[__name__]
   sys.modules.setdefault('taichi_splatting', me)
-  for sub in ('data_types', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
+  for sub in ('data_types', 'scene_io', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
               'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'optim', 'optim.fractional',

@@ -187,6 +187,17 @@ class Gaussians3D(TensorClass):
     return Gaussians3D(position=position, log_scaling=log_scale.unsqueeze(1).repeat(1, 3), rotation=rotation,
                        alpha_logit=alpha_logit, feature=feature, batch_size=(n,))
 
+  @staticmethod
+  def load_ply(path, *, device='cpu', sh_degree='file', chunk_rows: int = 1 << 20) -> 'Gaussians3D':
+    """A scene from a 3DGS PLY file (``scene_io.load_ply``: field mapping, formats and errors are described there)."""
+    from .scene_io import load_ply     # (numpy, file handling: kept out of the data model's import)
+    return load_ply(path, device=device, sh_degree=sh_degree, chunk_rows=chunk_rows)
+
+  def save_ply(self, path, *, chunk_rows: int = 1 << 20) -> None:
+    """Write the scene as a binary 3DGS PLY file (``scene_io.save_ply``)."""
+    from .scene_io import save_ply
+    save_ply(self, path, chunk_rows=chunk_rows)
+
 
 def inverse_sigmoid(x: torch.Tensor):
   return torch.log(x / (1 - x))

@@ -1,0 +1,113 @@
+#!/usr/bin/env python
+"""Render a 3DGS PLY scene: the door through which a scene that is not synthetic reaches the renderer and its measurements.
+
+Loads the scene onto the GPU (taichi_splatting_amd.scene_io), puts K pinhole cameras (60 degrees across the width) on a
+circle around the scene's robust centre — the median position; the circle lies in the x-z plane with +y down, the frame
+of a structure-from-motion reconstruction; its radius is 1.2 x the largest 5-95 % extent of the three axes — looking
+inwards, and calls render_gaussians(use_sh=True) on each.  Prints ONE JSON line: N, SH degree, the load time split into
+read (file -> pinned staging buffer, host seconds) and upload / unpack (device events), and per view the visible
+gaussians and tile overlaps; ms per frame is the median over the views after one warm-up pass over all of them.  With
+--out the images are written as view_000.npy ... (H, W, 3) float32.
+
+    python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR]
+"""
+import argparse
+import json
+import math
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+from taichi_splatting_amd import CameraParams, RasterConfig, frame, render_gaussians, scene_io     # noqa: E402
+
+
+def orbit_cameras(position, views, size, device):
+  """``views`` cameras on a circle around the median of ``position`` (N, 3), each looking at it; camera axes x right, y down,
+  z forward."""
+  w, h = size
+  ordered = position.sort(dim=0).values
+  n = ordered.shape[0]
+  centre = ordered[n // 2]
+  extent = float((ordered[min(n - 1, int(0.95 * n))] - ordered[int(0.05 * n)]).max())
+  radius = 1.2 * max(extent, 1e-3)
+  focal = 0.5 * w / math.tan(math.radians(30.0))
+  projection = torch.tensor([focal, focal, 0.5 * w, 0.5 * h], dtype=torch.float32, device=device)
+  down = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64)
+  cameras = []
+  for v in range(views):
+    angle = 2.0 * math.pi * v / views
+    eye = centre.double().cpu() + radius * torch.tensor([math.sin(angle), 0.0, -math.cos(angle)], dtype=torch.float64)
+    forward = centre.double().cpu() - eye
+    forward = forward / forward.norm()
+    right = torch.linalg.cross(down, forward)
+    right = right / right.norm()
+    T = torch.eye(4, dtype=torch.float64)
+    T[:3, :3] = torch.stack([right, torch.linalg.cross(forward, right), forward])
+    T[:3, 3] = -T[:3, :3] @ eye
+    cameras.append(CameraParams(projection=projection, T_camera_world=T.to(torch.float32).to(device),
+                                near_plane=0.01 * radius, far_plane=100.0 * radius, image_size=(w, h), id=v))
+  return cameras, radius
+
+
+def main():
+  p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+  p.add_argument('scene')
+  p.add_argument('--size', type=int, nargs=2, default=(1024, 768), metavar=('W', 'H'))
+  p.add_argument('--views', type=int, default=8)
+  p.add_argument('--out', default='')
+  args = p.parse_args()
+  if not torch.cuda.is_available():
+    sys.exit("render_scene: no GPU visible (the renderer has no CPU fallback)")
+  if args.views < 1:
+    sys.exit("render_scene: --views must be at least 1")
+  device = torch.device('cuda:0')
+  torch.empty(1, device=device)                     # context creation is not load time
+
+  timings = {}
+  start = time.perf_counter()
+  gaussians = scene_io._load(args.scene, device, 'file', 1 << 20, timings)
+  torch.cuda.synchronize()
+  load_s = time.perf_counter() - start
+  n = gaussians.position.shape[0]
+  if n == 0:
+    sys.exit(f"render_scene: {args.scene} holds no gaussians")
+  degree = math.isqrt(gaussians.feature.shape[2]) - 1
+  cameras, radius = orbit_cameras(gaussians.position, args.views, tuple(args.size), device)
+  config = RasterConfig()
+
+  visible, overlaps, frame_ms, images = [], [], [], []
+  with torch.no_grad():
+    for camera in cameras:                          # warm-up: every view once (capacities, mapper choice, allocator)
+      rendering = render_gaussians(gaussians, camera, config, use_sh=True)
+      visible.append(int(rendering.points.idx.shape[0]))
+      overlaps.append(int(frame.frame_status(rendering)['overlaps']) if hasattr(rendering, 'frame') else None)
+    torch.cuda.synchronize()
+    for camera in cameras:
+      begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      begin.record()
+      rendering = render_gaussians(gaussians, camera, config, use_sh=True)
+      end.record()
+      end.synchronize()
+      frame_ms.append(begin.elapsed_time(end))
+      images.append(rendering.image)
+  if args.out:
+    out = Path(args.out)
+    out.mkdir(parents=True, exist_ok=True)
+    for v, image in enumerate(images):
+      np.save(out / f'view_{v:03d}.npy', image.cpu().numpy())
+  print(json.dumps(dict(
+    scene=str(args.scene), n=n, sh_degree=degree, image_size=list(args.size), views=args.views, orbit_radius=round(radius, 6),
+    load_s=round(load_s, 4), read_s=round(timings['read_s'], 4), upload_ms=round(timings['upload_ms'], 3),
+    unpack_ms=round(timings['unpack_ms'], 3), visible=visible, overlaps=overlaps,
+    frame_ms=round(statistics.median(frame_ms), 4), frame_ms_per_view=[round(ms, 4) for ms in frame_ms],
+    images=str(args.out) if args.out else None)), flush=True)
+
+
+if __name__ == '__main__':
+  main()
