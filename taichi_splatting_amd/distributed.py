@@ -24,6 +24,7 @@ from typing import Callable, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from ._window import RowWindow
 from .data_types import Gaussians3D, RasterConfig
 from .perspective import CameraParams
 
@@ -133,8 +134,7 @@ def render_strip_step(gaussians: Gaussians3D, camera_params: CameraParams, confi
   rows = strip_rows(tiles_high, world_size, rank) if bounds is None else (int(bounds[rank]), int(bounds[rank + 1]))
   rendering = render_projected(indexes, g2, f2, depths.detach(), camera_params, config, tile_rows=rows)
 
-  px_rows = (rows[0] * ts, min(rows[1] * ts, camera_params.image_size[1]))
-  loss = loss_fn(rendering.image, px_rows)
+  loss = loss_fn(rendering.image, RowWindow.of(camera_params.image_size, ts, rows).px_rows)
   if backward and (g2.requires_grad or f2.requires_grad):
     # participation in the all-reduce below does not depend on what loss_fn returned on this rank: a constant
     # loss simply contributes zeros
@@ -492,9 +492,7 @@ def render_sharded_step(shard: Gaussians3D, camera_params: CameraParams, config:
                       all_to_all_backward_sent_bytes=received * (7 + f) * es if backward else 0,
                       all_to_all_backward_received_bytes=sent * (7 + f) * es if backward else 0)
 
-  h = camera_params.image_size[1]
-  px_rows = (min(rows[0] * ts, h), min(rows[1] * ts, h))
-  loss = loss_fn(rendering.image, px_rows)
+  loss = loss_fn(rendering.image, RowWindow.of(camera_params.image_size, ts, rows).px_rows)
   if backward and (g2.requires_grad or f2.requires_grad):
     # the reverse all-to-all in _StripExchange.backward is a collective: every rank runs it, also one whose
     # loss_fn returned a constant (empty strip)

@@ -22,7 +22,7 @@ import collections
 import ctypes
 from dataclasses import dataclass, replace
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 import weakref
 
 import torch
@@ -31,6 +31,7 @@ from . import _lib
 # (re-exported: callers, tests and tools reach the moved names through this module)
 from ._frame_host import (GRAPH_K_WORDS, K_PENDING, K_SLOTS, MOMENTS_LRU, KSlots, _drop_moments, _k_host, _lock, _moments,
                           _moments_buffer, _moments_pinned, k_ring, parked_gc, pinned_word, release_moments, wait_for_k)   # noqa: F401
+from ._window import RowWindow
 from .data_types import RasterConfig
 
 # MS_FRAME=legacy: render_gaussians composes the modular operators (project_to_image, evaluate_sh_at, map_to_tiles,
@@ -263,6 +264,14 @@ def identity_indexes(n: int, device) -> torch.Tensor:
   return cached
 
 
+class DeferredVisibility(NamedTuple):
+  """what the on-demand visibility pass of a frame needs (detached views: no cycle through the autograd node)"""
+  visibility: torch.Tensor
+  points7: torch.Tensor
+  colours: torch.Tensor
+  config: RasterConfig
+
+
 class FrameState:
   """What one frame keeps between its forward pass, its backward pass and the lazily built ``points``."""
 
@@ -275,7 +284,8 @@ class FrameState:
     self.k = None                 # overlap total (eager mode), None under graph capture
     self.capacity = 0
     self.children = []            # (weakref to a tensor handed out, index list or None, 'points7' | 'colours')
-    self.y0 = 0
+    self.window = None            # RowWindow: the rows the frame renders and stores
+    self.placeholder = None       # stands in for the images of a window that stores no row (RowWindow.placeholder)
     self.pending = None           # eager mode: the PendingFrame = the look at K + capacity check, run once (by the frame's
                                   # caller, or later)
     self.k_peek = None            # numpy view of the frame's pinned K word while `pending` is set
@@ -288,7 +298,7 @@ class FrameState:
     self.colours_ready = None     # event behind the SH pass on the executor's second stream (SH_SIDE_STREAM)
     self.vis_deferred = False     # the forward ran without visibility: the backward writes it (VISIBILITY_FROM_BACKWARD)
     self.vis_ready = True
-    self.vis_args = None          # what the on-demand pass needs (detached views: no cycle through the autograd node)
+    self.vis_pass = None          # DeferredVisibility while `vis_deferred`
 
   def ensure_visibility(self):
     """A deferred visibility (VISIBILITY_FROM_BACKWARD) that is read before the backward pass wrote it: the forward's
@@ -296,25 +306,31 @@ class FrameState:
     global visibility_passes
     if not self.vis_deferred or self.vis_ready:
       return
-    visibility, points7, colours, w, h, f, rows, y0, y1, config = self.vis_args
+    vis = self.vis_pass
     self.settle()
     self.vis_ready = True
     visibility_passes += 1
-    if y1 <= y0 or points7.shape[0] == 0 or self.capacity == 0 or self.keep_k is None:
+    if vis.points7.shape[0] == 0 or self.capacity == 0 or self.keep_k is None:
       return
-    lib = _lib.load()
-    dtype, device = points7.dtype, points7.device
-    cfg_v = _lib.raster_config_c(replace(config, compute_visibility=True, compute_point_heuristic=False))
-    es = points7.element_size()
     with torch.no_grad():
-      image = torch.empty((y1 - y0, w, f), dtype=dtype, device=device)
-      alpha = torch.empty((y1 - y0, w), dtype=dtype, device=device)
-      visibility.zero_()
-      _lib.check(lib.ms_raster_fwd(points7.data_ptr(), colours.data_ptr(), self.tile_ranges().data_ptr(),
-                                   self.overlap_to_point().data_ptr(), w, h, f, cfg_v,
-                                   image.data_ptr() - y0 * w * f * es, alpha.data_ptr() - y0 * w * es, visibility.data_ptr(),
-                                   rows[0], rows[1], _lib.dtype_code(dtype), _lib.current_stream(device)),
-                 "render_gaussians (visibility on demand)")
+      vis.visibility.zero_()
+      self.raster_kept_lists(vis.points7, vis.colours, vis.colours.shape[1],
+                             replace(vis.config, compute_visibility=True, compute_point_heuristic=False), vis.visibility,
+                             "render_gaussians (visibility on demand)", scratch=True)
+
+  def raster_kept_lists(self, points7, features, f, config, visibility, what, scratch=False):
+    """One ``ms_raster_fwd`` pass over the frame's window on its kept tile lists: ``features`` (n, f) blended under
+    ``config`` into a new image (stored rows, w, f), which is returned (``scratch``: wanted for ``visibility`` only)."""
+    window, dtype, device = self.window, points7.dtype, points7.device
+    image = window.alloc(dtype, device, f, scratch=scratch)
+    alpha = window.alloc(dtype, device, scratch=True)
+    hold = window.placeholder(dtype, device)
+    _lib.check(_lib.load().ms_raster_fwd(points7.data_ptr(), features.data_ptr(), self.tile_ranges().data_ptr(),
+                                         self.overlap_to_point().data_ptr(), window.w, window.h, f, _lib.raster_config_c(config),
+                                         window.base(image, f, hold), window.base(alpha, 1, hold), _lib.ptr(visibility),
+                                         window.rows[0], window.rows[1], _lib.dtype_code(dtype), _lib.current_stream(device)),
+               what)
+    return image
 
   def settle(self):
     """Look at the frame's overlap total (waiting for it if the GPU has not produced it yet) and re-run the emission
@@ -382,10 +398,7 @@ def byte_block(nbytes, device):
 def frame_desc(n, image_size, dtype, f, sh_degree, config, depth_range=(0.0, 0.0), tile_rows=None, projected=False,
                capacity=0, depth16=False):
   """(ms_frame_desc of a frame, the tile rows it renders)"""
-  w, h = int(image_size[0]), int(image_size[1])
-  ts = config.tile_size
-  tiles_high = (h + ts - 1) // ts
-  rows = (0, tiles_high) if tile_rows is None else (max(0, int(tile_rows[0])), min(tiles_high, int(tile_rows[1])))
+  w, h, rows = RowWindow.of(image_size, config.tile_size, tile_rows)[:3]
   return _lib.FrameDescC(n=int(n), k_capacity=int(capacity), image_w=w, image_h=h, dtype=_lib.dtype_code(dtype), f=int(f),
                          sh_degree=int(sh_degree), depth16=int(depth16), tile_row_begin=rows[0], tile_row_end=rows[1],
                          projected_input=int(projected), mapper=0, near_plane=float(depth_range[0]),
@@ -424,6 +437,57 @@ def attach_moments(gr, g_image, device, n, det):
   return fixed_exp
 
 
+def gaussian_inputs(position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, use_sh: bool):
+  """(the seven tensors detached and contiguous, the ms_frame_inputs pointing at them — valid while the list lives —,
+  colour channels f, SH degree or -1 for plain colours)"""
+  tensors = [t.detach().contiguous() for t in
+             (position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection)]
+  pos, lsc, rot, alog, feat, Tcw, proj = tensors
+  if use_sh:
+    assert feat.ndim == 3, f"SH features must have 3 dimensions, got {feat.shape}"
+    f, d = feat.shape[1], feat.shape[2]
+    degree = int(round(d ** 0.5)) - 1
+    assert (degree + 1) ** 2 == d, f"SH feature count must be square, got {d} ({feat.shape})"
+    assert 0 <= degree <= 3, f"SH degree must be between 0 and 3, got {degree}"
+  else:
+    assert feat.ndim == 2, f"Features must be (N, C) if use_sh=False, got {feat.shape}"
+    f, degree = feat.shape[1], -1
+  inputs = _lib.FrameInputsC(position=pos.data_ptr(), log_scaling=lsc.data_ptr(), rotation=rot.data_ptr(),
+                             alpha_logit=alog.data_ptr(), feature=feat.data_ptr(), T_camera_world=Tcw.data_ptr(),
+                             projection=proj.data_ptr(), points7=None, depth=None, colours=None)
+  return tensors, inputs, f, degree
+
+
+def gaussian_grads(gr, tensors, need, feature_from_kernel: bool):
+  """Allocate what the per-gaussian backward pass writes and point ``gr`` at it: the gradients of position, log_scaling,
+  rotation and alpha_logit wanted by ``need[:4]`` and, with ``need[4]``, the feature gradient when the kernel is the one
+  that writes it (SH colours; plain colours on the moments path of a whole backward) — otherwise the caller's array of
+  colour gradients IS the feature gradient.  Returns ([four gradients or None], grad_feature or None)."""
+  grads = [torch.empty_like(t) if need[i] else None for i, t in enumerate(tensors[:4])]
+  gr.grad_position, gr.grad_log_scaling, gr.grad_rotation, gr.grad_alpha_logit = (_lib.ptr(t) for t in grads)
+  grad_feature = None
+  if need[4] and feature_from_kernel:
+    grad_feature = torch.empty_like(tensors[4])
+    gr.grad_feature = grad_feature.data_ptr()
+  return grads, grad_feature
+
+
+def image_grad(gr, g_image, moments_path: bool, window: RowWindow, channels: int, placeholder=None):
+  """dL/dimage of a raster backward over ``window``.  A sum / mean loss hands autograd an EXPANDED scalar (strides 0): the
+  moments kernel then reads one pixel's values (``grad_image_broadcast``) instead of a (rows, w, channels) copy that
+  .contiguous() would write and the kernel read back (50 MB at 2048^2).  Returns the tensor that must stay alive."""
+  broadcast = (BROADCAST_GRAD and moments_path and g_image.dim() == 3 and g_image.shape[0] * g_image.shape[1] > 1
+               and g_image.stride(0) == 0 and g_image.stride(1) == 0)
+  if broadcast:
+    keep = g_image[0, 0].contiguous()                        # (channels,)
+    gr.grad_image = keep.data_ptr()
+  else:
+    keep = g_image.contiguous()
+    gr.grad_image = window.base(keep, channels, placeholder)
+  gr.grad_image_broadcast = int(broadcast)
+  return keep
+
+
 def _enqueue_backward(state, gr, device, what):
   try:
     with _lock:       # the two launches of a backward pass are enqueued back to back (ctypes releases the GIL)
@@ -432,10 +496,6 @@ def _enqueue_backward(state, gr, device, what):
   except Exception:
     _drop_moments()         # the accumulator rows may have been left half-written: start from a fresh buffer
     raise
-
-
-def _strip_pixels(rows, tile_size, h):
-  return min(rows[0] * tile_size, h), min(rows[1] * tile_size, h)
 
 
 class PendingFrame:
@@ -657,52 +717,23 @@ class _FrameFunction(torch.autograd.Function):
               opts: FrameOptions, state: FrameState):
     lib = _lib.load()
     _lib.require_gpu(position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection)
-    tensors = [t.detach().contiguous() for t in
-               (position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection)]
-    pos, lsc, rot, alog, feat, Tcw, proj = tensors
+    tensors, inputs, f, degree = gaussian_inputs(position, log_scaling, rotation, alpha_logit, feature, T_camera_world,
+                                                 projection, opts.use_sh)
+    pos, feat = tensors[0], tensors[4]
     dtype, device = pos.dtype, pos.device
     assert all(t.dtype == dtype for t in tensors), "render_gaussians: all inputs must share one dtype"
     config = opts.config
     n = pos.shape[0]
-    w, h = int(opts.image_size[0]), int(opts.image_size[1])
-    ts = config.tile_size
+    window = RowWindow.of(opts.image_size, config.tile_size, opts.tile_rows, opts.crop_to_rows)
 
-    if opts.use_sh:
-      assert feat.ndim == 3, f"SH features must have 3 dimensions, got {feat.shape}"
-      f, d = feat.shape[1], feat.shape[2]
-      degree = int(round(d ** 0.5)) - 1
-      assert (degree + 1) ** 2 == d, f"SH feature count must be square, got {d} ({feat.shape})"
-      assert 0 <= degree <= 3, f"SH degree must be between 0 and 3, got {degree}"
-    else:
-      assert feat.ndim == 2, f"Features must be (N, C) if use_sh=False, got {feat.shape}"
-      f, degree = feat.shape[1], -1
-
-    key = _shape_key(device, n, (w, h), config, opts.tile_rows, opts.use_depth16)
-    desc, rows = frame_desc(n, (w, h), dtype, f, degree, config, opts.depth_range, opts.tile_rows, depth16=opts.use_depth16)
-    stream = _lib.current_stream(device)
-    inputs = _lib.FrameInputsC(position=pos.data_ptr(), log_scaling=lsc.data_ptr(), rotation=rot.data_ptr(),
-                               alpha_logit=alog.data_ptr(), feature=feat.data_ptr(), T_camera_world=Tcw.data_ptr(),
-                               projection=proj.data_ptr(), points7=None, depth=None, colours=None)
-
-    # images: with crop_to_rows only the strip's pixel rows exist; the kernels address absolute rows, so they get the
-    # address row 0 WOULD have (they touch rows [y0, y1) only)
-    y0, y1 = _strip_pixels(rows, ts, h) if opts.crop_to_rows else (0, h)
-    image = torch.empty((y1 - y0, w, f), dtype=dtype, device=device)
-    alpha = torch.empty((y1 - y0, w), dtype=dtype, device=device)
-    whole = rows == (0, (h + ts - 1) // ts)
-    if not opts.crop_to_rows and not whole:
-      image.zero_(); alpha.zero_()
+    key = _shape_key(device, n, (window.w, window.h), config, opts.tile_rows, opts.use_depth16)
+    desc, _ = frame_desc(n, opts.image_size, dtype, f, degree, config, opts.depth_range, opts.tile_rows,
+                         depth16=opts.use_depth16)
+    image, alpha = window.alloc(dtype, device, f), window.alloc(dtype, device)
     visibility, heuristic = _point_outputs(n, config, dtype, device)
-    es = image.element_size()
-    state.y0 = y0
+    state.window, state.placeholder = window, window.placeholder(dtype, device)
     state.tensors = tensors                                  # the pointers in `inputs` stay valid
-    if y1 > y0:
-      image_ptr, alpha_ptr = image.data_ptr() - y0 * w * f * es, alpha.data_ptr() - y0 * w * es
-    else:
-      # an empty cropped strip: zero-row tensors have a null data pointer, which the C entry points reject (and
-      # `0 - y0 * ...` would wrap); the raster touches no row, any valid address will do
-      state.dummy = torch.empty((16,), dtype=dtype, device=device)
-      image_ptr = alpha_ptr = state.dummy.data_ptr()
+    image_ptr, alpha_ptr = window.base(image, f, state.placeholder), window.base(alpha, 1, state.placeholder)
     # a frame that will be differentiated may take its visibility from the backward pass (VISIBILITY_FROM_BACKWARD)
     defer_vis = bool(state.vis_deferred and config.compute_visibility and config.compute_point_heuristic and n > 0
                      and lib.ms_frame_uses_moments(ctypes.byref(desc), 0))
@@ -716,28 +747,19 @@ class _FrameFunction(torch.autograd.Function):
     depth = block_view(keep_n, layout.depth, dtype, (n,))
     colours = block_view(keep_n, layout.colours, dtype, (n, f)) if opts.use_sh else None
     if defer_vis:
-      state.vis_args = (visibility.detach(), points7.detach(), (colours if opts.use_sh else feat).detach(), w, h, f, rows,
-                        y0, y1, config)
+      state.vis_pass = DeferredVisibility(visibility.detach(), points7.detach(), (colours if opts.use_sh else feat).detach(),
+                                          config)
 
     median = None
     if opts.render_median_depth:
       # renderer.py:77-82: quantile pass over the depths with the same tile lists
-      cfg_m = _lib.raster_config_c(replace(config, use_alpha_blending=False, saturate_threshold=config.median_threshold,
-                                           compute_visibility=False, compute_point_heuristic=False))
-      median = torch.empty((y1 - y0, w, 1), dtype=dtype, device=device)
-      median_alpha = torch.empty((y1 - y0, w), dtype=dtype, device=device)
-      if not opts.crop_to_rows and not whole:
-        median.zero_()
-      if y1 > y0:
-        _lib.check(lib.ms_raster_fwd(points7.data_ptr(), depth.data_ptr(), state.tile_ranges().data_ptr(),
-                                     state.overlap_to_point().data_ptr(), w, h, 1, cfg_m,
-                                     median.data_ptr() - y0 * w * es, median_alpha.data_ptr() - y0 * w * es, None,
-                                     rows[0], rows[1], _lib.dtype_code(dtype), stream), "render_gaussians (median depth)")
-      median = median.squeeze(-1)
+      cfg_m = replace(config, use_alpha_blending=False, saturate_threshold=config.median_threshold,
+                      compute_visibility=False, compute_point_heuristic=False)
+      median = state.raster_kept_lists(points7, depth, 1, cfg_m, None, "render_gaussians (median depth)").squeeze(-1)
 
     ctx.set_materialize_grads(False)
     ctx.state, ctx.opts = state, opts
-    ctx.f, ctx.degree, ctx.rows = f, degree, rows
+    ctx.f, ctx.degree = f, degree
     ctx.save_for_backward(*tensors, image)
     ctx.heuristic = heuristic
     non_diff = [alpha, visibility, heuristic] + ([median] if median is not None else [])
@@ -761,17 +783,8 @@ class _FrameFunction(torch.autograd.Function):
       zeros = [torch.zeros_like(t) if need[i] else None for i, t in enumerate((pos, lsc, rot, alog, feat, Tcw, proj))]
       return (*zeros, None, None)
 
-    w, h = opts.image_size
     stream = _lib.current_stream(device)
     moments_path, det = backward_mode(desc)
-    # dL/dimage of a sum / mean loss arrives as an EXPANDED scalar (strides 0): the moments kernel reads one pixel's f
-    # values instead of an (H, W, f) copy that .contiguous() would write and the kernel read back (50 MB at 2048^2)
-    broadcast = (BROADCAST_GRAD and moments_path and g_image is not None and g_image.dim() == 3 and g_image.shape[0] * g_image.shape[1] > 1
-                 and g_image.stride(0) == 0 and g_image.stride(1) == 0)
-    if broadcast:
-      g_image = g_image[0, 0].contiguous()                     # (f,)
-    else:
-      g_image = g_image.contiguous() if g_image is not None else torch.zeros_like(image)
     retained = state.retained()
     want_points = any(kind == 'points7' for _, _, kind in retained)
     # camera pose optimisation with SH colours: the view direction depends on the camera position =
@@ -781,10 +794,8 @@ class _FrameFunction(torch.autograd.Function):
     want_colours = any(kind == 'colours' for _, _, kind in retained) or sh_camera
 
     gr = _lib.FrameGradsC()
-    row_bytes = state.y0 * w * image.element_size()          # cropped strip: address of the (absent) row 0
-    gr.image = image.data_ptr() - row_bytes * f
-    gr.grad_image = g_image.data_ptr() - (0 if broadcast else row_bytes * f)
-    gr.grad_image_broadcast = int(broadcast)
+    gr.image = state.window.base(image, f)
+    g_image = image_grad(gr, g_image if g_image is not None else torch.zeros_like(image), moments_path, state.window, f)
     extras = []
     for name, g in (('extra_points7', g_points7), ('extra_depth', g_depth), ('extra_colours', g_colours)):
       if g is not None:
@@ -804,23 +815,17 @@ class _FrameFunction(torch.autograd.Function):
       grad_colours = torch.zeros((n, f), dtype=dtype, device=device)
     gr.grad_points7, gr.grad_colours = _lib.ptr(grad_points7), _lib.ptr(grad_colours)
 
-    grads = [torch.empty_like(t) if need[i] else None for i, t in enumerate((pos, lsc, rot, alog))]
-    gr.grad_position, gr.grad_log_scaling, gr.grad_rotation, gr.grad_alpha_logit = (_lib.ptr(t) for t in grads)
-    grad_feature = None
-    if need[4]:
-      if opts.use_sh or moments_path:
-        grad_feature = torch.empty_like(feat)
-        gr.grad_feature = grad_feature.data_ptr()
-      else:
-        grad_feature = grad_colours                 # plain colours: the raster backward's accumulator IS the gradient
+    grads, grad_feature = gaussian_grads(gr, (pos, lsc, rot, alog, feat), need, opts.use_sh or moments_path)
+    if need[4] and grad_feature is None:
+      grad_feature = grad_colours                   # plain colours: the raster backward's accumulator IS the gradient
     need_camera = need[5] or need[6]
     grad_camera = torch.zeros((16,), dtype=dtype, device=device) if need_camera else None
     gr.grad_camera = _lib.ptr(grad_camera)
     if config.compute_point_heuristic:
       gr.point_heuristic = ctx.heuristic.data_ptr()
-    vis_here = state.vis_deferred and moments_path and state.vis_args is not None
+    vis_here = state.vis_deferred and moments_path and state.vis_pass is not None
     if vis_here:
-      gr.point_visibility = state.vis_args[0].data_ptr()
+      gr.point_visibility = state.vis_pass.visibility.data_ptr()
     elif state.vis_deferred:
       state.ensure_visibility()           # (a backward that cannot deliver it: not on the moments path after all)
 

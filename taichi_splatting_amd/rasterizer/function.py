@@ -12,6 +12,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from .. import _lib
+from .._window import RowWindow
 from ..data_types import RasterConfig
 from ..mapper.tile_mapper import map_to_tiles
 
@@ -40,34 +41,15 @@ def _use_moments_backward(config: RasterConfig, dtype, f: int) -> bool:
   return dtype == torch.float32 and f == 3 and not config.antialias and os.environ.get('MS_RASTER_BWD', 'scan') != 'patch'
 
 
-def _tile_rows(config: RasterConfig, image_size, tile_rows):
-  tiles_high = (image_size[1] + config.tile_size - 1) // config.tile_size
-  if tile_rows is None:
-    return 0, tiles_high
-  return max(0, int(tile_rows[0])), min(tiles_high, int(tile_rows[1]))
-
-
-def _strip_pixels(rows, tile_size, h):
-  """Pixel rows [y0, y1) covered by the tile rows ``rows``."""
-  return min(rows[0] * tile_size, h), min(rows[1] * tile_size, h)
-
-
-def _forward_chunk(lib, gaussians, features, ranges, o2p, image_size, cfg_c, visibility, rows, stream, crop):
-  w, h = image_size
+def _forward_chunk(lib, gaussians, features, ranges, o2p, window, cfg_c, visibility, stream):
   f = features.shape[1]
-  dtype = gaussians.dtype
-  y0, y1 = _strip_pixels(rows, cfg_c.tile_size, h) if crop else (0, h)
-  # cropped: only the strip's pixel rows exist; the kernels address absolute rows, so they get the
-  # address row 0 WOULD have (they touch rows [y0, y1) only)
-  image = torch.empty((y1 - y0, w, f), dtype=dtype, device=gaussians.device)
-  alpha = torch.empty((y1 - y0, w), dtype=dtype, device=gaussians.device)
-  if not crop and rows != (0, (h + cfg_c.tile_size - 1) // cfg_c.tile_size):
-    image.zero_(); alpha.zero_()   # rows outside the strip are not rendered
-  if y1 > y0:
-    _lib.check(lib.ms_raster_fwd(gaussians.data_ptr(), features.data_ptr(), ranges.data_ptr(), _lib.ptr(o2p),
-                                 w, h, f, cfg_c, image.data_ptr() - y0 * w * f * image.element_size(),
-                                 alpha.data_ptr() - y0 * w * alpha.element_size(), _lib.ptr(visibility),
-                                 rows[0], rows[1], _lib.dtype_code(dtype), stream), "rasterize forward")
+  dtype, device = gaussians.dtype, gaussians.device
+  image, alpha = window.alloc(dtype, device, f), window.alloc(dtype, device)   # rows outside the strip are not rendered
+  hold = window.placeholder(dtype, device)
+  _lib.check(lib.ms_raster_fwd(gaussians.data_ptr(), features.data_ptr(), ranges.data_ptr(), _lib.ptr(o2p),
+                               window.w, window.h, f, cfg_c, window.base(image, f, hold), window.base(alpha, 1, hold),
+                               _lib.ptr(visibility), window.rows[0], window.rows[1], _lib.dtype_code(dtype), stream),
+             "rasterize forward")
   return image, alpha
 
 
@@ -98,7 +80,7 @@ class _RasterFunction(torch.autograd.Function):
 
     device, dtype = gaussians.device, gaussians.dtype
     n, f = features_c.shape
-    rows = _tile_rows(config, (w, h), tile_rows)
+    window = RowWindow.of((w, h), ts, tile_rows, crop_to_rows)
     stream = _lib.current_stream(device)
     cfg_c = _lib.raster_config_c(config)
 
@@ -119,8 +101,8 @@ class _RasterFunction(torch.autograd.Function):
       visibility = torch.empty((0,), dtype=dtype, device=device)
 
     if f <= MAX_KERNEL_FEATURES:
-      image, alpha = _forward_chunk(lib, gaussians_c, features_c, ranges, o2p, (w, h), cfg_c,
-                                    visibility if config.compute_visibility else None, rows, stream, crop_to_rows)
+      image, alpha = _forward_chunk(lib, gaussians_c, features_c, ranges, o2p, window, cfg_c,
+                                    visibility if config.compute_visibility else None, stream)
     else:
       # channels are independent in the forward pass: render them MAX_KERNEL_FEATURES at a time
       images = []
@@ -128,8 +110,7 @@ class _RasterFunction(torch.autograd.Function):
         chunk = features_c[:, c0:c0 + MAX_KERNEL_FEATURES].contiguous()
         vis = visibility if (config.compute_visibility and c0 == 0) else None
         cfg_chunk = cfg_c if c0 == 0 else _lib.raster_config_c(replace(config, compute_visibility=False))
-        img, alpha_c = _forward_chunk(lib, gaussians_c, chunk, ranges, o2p, (w, h), cfg_chunk, vis, rows, stream,
-                                      crop_to_rows)
+        img, alpha_c = _forward_chunk(lib, gaussians_c, chunk, ranges, o2p, window, cfg_chunk, vis, stream)
         images.append(img)
         if c0 == 0:
           alpha = alpha_c
@@ -138,10 +119,8 @@ class _RasterFunction(torch.autograd.Function):
     ctx.set_materialize_grads(False)      # no zero tensors for image_weight / heuristics / visibility gradients
     ctx.overlap_to_point = o2p
     ctx.tile_overlap_ranges = ranges
-    ctx.image_size = (w, h)
     ctx.config = config
-    ctx.rows = rows
-    ctx.y0 = _strip_pixels(rows, ts, h)[0] if crop_to_rows else 0
+    ctx.window = window
     ctx.point_heuristic = point_heuristic
     ctx.mark_non_differentiable(alpha, point_heuristic, visibility)
     ctx.save_for_backward(gaussians_c, features_c, image)
@@ -151,8 +130,7 @@ class _RasterFunction(torch.autograd.Function):
   def backward(ctx, grad_image, grad_alpha, grad_point_heuristic, grad_visibility):
     lib = _lib.load()
     gaussians, features, image = ctx.saved_tensors
-    config = ctx.config
-    w, h = ctx.image_size
+    config, window = ctx.config, ctx.window
     n, f = features.shape
     need_points, need_features = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
 
@@ -165,21 +143,27 @@ class _RasterFunction(torch.autograd.Function):
     grad_features = alloc(features) if need_features else None
 
     grad_image = grad_image.contiguous()
-    if image.shape[0] == 0:
-      return grad_gaussians, grad_features, None, None, None, None, None, None
-    row_bytes = ctx.y0 * w * image.element_size()      # cropped strip: address of the (absent) row 0
+    hold = window.placeholder(gaussians.dtype, gaussians.device)
     stream = _lib.current_stream(gaussians.device)
     dtype_code = _lib.dtype_code(gaussians.dtype)
     cfg_c = _lib.raster_config_c(config)
+
+    def launch(feat, img, gimg, gfeat, heur):
+      """the generic kernels on ``feat.shape[1]`` channels; accumulates into grad_gaussians, gfeat and heur"""
+      fc = feat.shape[1]
+      _lib.check(lib.ms_raster_bwd(gaussians.data_ptr(), feat.data_ptr(), ctx.tile_overlap_ranges.data_ptr(),
+                                   _lib.ptr(ctx.overlap_to_point), window.base(img, fc, hold), window.base(gimg, fc, hold),
+                                   window.w, window.h, fc, cfg_c, _lib.ptr(grad_gaussians), _lib.ptr(gfeat), _lib.ptr(heur),
+                                   window.rows[0], window.rows[1], dtype_code, stream), "rasterize backward")
 
     if moments_path:
       det = int(DETERMINISTIC_BACKWARD)
       moments = torch.zeros((n, _lib.MOMENT_ROW), dtype=torch.int64 if det else torch.float32, device=gaussians.device)
       fixed_exp = _lib.fixed_point_exponents(grad_image) if det else None
       _lib.check(lib.ms_raster_bwd_moments(gaussians.data_ptr(), features.data_ptr(), ctx.tile_overlap_ranges.data_ptr(),
-                                           _lib.ptr(ctx.overlap_to_point), image.data_ptr() - row_bytes * f,
-                                           grad_image.data_ptr() - row_bytes * f, w, h, cfg_c, moments.data_ptr(), det,
-                                           _lib.ptr(fixed_exp), ctx.rows[0], ctx.rows[1], stream), "rasterize backward")
+                                           _lib.ptr(ctx.overlap_to_point), window.base(image, f), window.base(grad_image, f),
+                                           window.w, window.h, cfg_c, moments.data_ptr(), det, _lib.ptr(fixed_exp),
+                                           window.rows[0], window.rows[1], stream), "rasterize backward")
       _lib.check(lib.ms_raster_moments_finalize(gaussians.data_ptr(), moments.data_ptr(), det, _lib.ptr(fixed_exp), n, _lib.ptr(grad_gaussians),
                                                 _lib.ptr(grad_features), _lib.ptr(heuristic), stream),
                  "rasterize backward (moments -> gradients)")
@@ -191,19 +175,11 @@ class _RasterFunction(torch.autograd.Function):
       pad = lambda t: torch.nn.functional.pad(t, (0, fw - f)).contiguous()
       feat_w, img_w, gimg_w = pad(features), pad(image), pad(grad_image)
       gfeat_w = torch.zeros_like(feat_w) if need_features else None
-      _lib.check(lib.ms_raster_bwd(gaussians.data_ptr(), feat_w.data_ptr(), ctx.tile_overlap_ranges.data_ptr(),
-                                   _lib.ptr(ctx.overlap_to_point), img_w.data_ptr() - row_bytes * fw,
-                                   gimg_w.data_ptr() - row_bytes * fw, w, h, fw, cfg_c, _lib.ptr(grad_gaussians),
-                                   _lib.ptr(gfeat_w), _lib.ptr(heuristic), ctx.rows[0], ctx.rows[1], dtype_code, stream),
-                 "rasterize backward")
+      launch(feat_w, img_w, gimg_w, gfeat_w, heuristic)
       if need_features:
         grad_features.copy_(gfeat_w[:, :f])
     elif f <= MAX_KERNEL_FEATURES:
-      _lib.check(lib.ms_raster_bwd(gaussians.data_ptr(), features.data_ptr(), ctx.tile_overlap_ranges.data_ptr(),
-                                   _lib.ptr(ctx.overlap_to_point), image.data_ptr() - row_bytes * f,
-                                   grad_image.data_ptr() - row_bytes * f, w, h, f, cfg_c, _lib.ptr(grad_gaussians), _lib.ptr(grad_features),
-                                   _lib.ptr(heuristic), ctx.rows[0], ctx.rows[1], dtype_code, stream),
-                 "rasterize backward")
+      launch(features, image, grad_image, grad_features, heuristic)
     else:
       # d(alpha) = sum_c (...)_c * G_c is linear in the channels, so point gradients of channel
       # chunks add up exactly (no heuristics on this path: see above).
@@ -213,11 +189,7 @@ class _RasterFunction(torch.autograd.Function):
         img_c = image[:, :, sl].contiguous()
         gimg_c = grad_image[:, :, sl].contiguous()
         gfeat_c = torch.zeros_like(feat_c) if need_features else None
-        _lib.check(lib.ms_raster_bwd(gaussians.data_ptr(), feat_c.data_ptr(), ctx.tile_overlap_ranges.data_ptr(),
-                                     _lib.ptr(ctx.overlap_to_point), img_c.data_ptr() - row_bytes * feat_c.shape[1],
-                                     gimg_c.data_ptr() - row_bytes * feat_c.shape[1], w, h, feat_c.shape[1], cfg_c, _lib.ptr(grad_gaussians), _lib.ptr(gfeat_c),
-                                     None, ctx.rows[0], ctx.rows[1],
-                                     dtype_code, stream), "rasterize backward")
+        launch(feat_c, img_c, gimg_c, gfeat_c, None)
         if need_features:
           grad_features[:, sl] = gfeat_c
 

@@ -29,6 +29,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, frame
+from ._window import RowWindow
 from .data_types import Gaussians3D, RasterConfig
 from .perspective import CameraParams
 
@@ -92,17 +93,6 @@ class StageTimer:
     return {k: round(v / max(self.steps, 1), 4) for k, v in self.totals.items()}
 
 
-def _feature_shape(feature: torch.Tensor, use_sh: bool):
-  if use_sh:
-    assert feature.ndim == 3, f"SH features must have 3 dimensions, got {feature.shape}"
-    d = feature.shape[2]
-    degree = int(round(d ** 0.5)) - 1
-    assert (degree + 1) ** 2 == d and 0 <= degree <= 3, f"SH feature count must be 1, 4, 9 or 16, got {d}"
-    return feature.shape[1], degree
-  assert feature.ndim == 2, f"Features must be (N, C) if use_sh=False, got {feature.shape}"
-  return feature.shape[1], -1
-
-
 def _accumulate(leaf: torch.Tensor, grad: Optional[torch.Tensor]):
   if grad is None or not leaf.requires_grad:
     return
@@ -126,8 +116,8 @@ class _RankStep:
     assert len(self.bounds) == world + 1 and self.bounds[0] == 0 and self.bounds[-1] == self.tiles_high, \
       f"bounds must run from 0 to tiles_high = {self.tiles_high} over {world} ranks, got {self.bounds}"
     self.rows = (self.bounds[rank], self.bounds[rank + 1])
-    h = self.image_size[1]
-    self.px_rows = (min(self.rows[0] * ts, h), min(self.rows[1] * ts, h))
+    self.window = RowWindow.of(self.image_size, ts, self.rows, cropped=True)     # a rank stores its strip's rows only
+    self.px_rows = self.window.px_rows
     self.k_capacity = 0
     self.timer = StageTimer(time_stages)
     # Overflow indicators live in PINNED HOST memory the kernels write through (like the eager frame's K word): the
@@ -160,21 +150,13 @@ class _RankStep:
     keep_k, scratch_k = frame.byte_block(lay.keep_k_bytes, device), frame.byte_block(lay.scratch_k_bytes, device)
     _lib.check(lib.ms_frame_project_count(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), scratch_n.data_ptr(),
                                           self.k_word.data_ptr(), None, stream), "rank step (map)")
-    w = self.image_size[0]
-    y0, y1 = self.px_rows
-    image = torch.empty((y1 - y0, w, f), dtype=dtype, device=device)
-    alpha = torch.empty((y1 - y0, w), dtype=dtype, device=device)
-    es = image.element_size()
-    if y1 > y0:
-      image_ptr, alpha_ptr = image.data_ptr() - y0 * w * f * es, alpha.data_ptr() - y0 * w * es
-    else:
-      # an empty strip (bounds may repeat a value): the mapper still runs (capacity, counters), the raster touches no
-      # row; zero-row tensors have a null data pointer, which the C entry points reject
-      self._dummy = torch.empty((16,), dtype=dtype, device=device)
-      image_ptr = alpha_ptr = self._dummy.data_ptr()
+    window = self.window
+    image, alpha = window.alloc(dtype, device, f), window.alloc(dtype, device)
+    # an empty strip (bounds may repeat a value): the mapper still runs (capacity, counters), the raster touches no row
+    self._placeholder = window.placeholder(dtype, device)
     _lib.check(lib.ms_frame_map_raster(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), scratch_n.data_ptr(),
-                                       keep_k.data_ptr(), scratch_k.data_ptr(), image_ptr, alpha_ptr, None, stream),
-               "rank step (raster)")
+                                       keep_k.data_ptr(), scratch_k.data_ptr(), window.base(image, f, self._placeholder),
+                                       window.base(alpha, 1, self._placeholder), None, stream), "rank step (raster)")
     self.last_counters = keep_n[lay.counters:lay.counters + 32].view(torch.int32)
     return lay, keep_n, keep_k, image, alpha
 
@@ -188,21 +170,12 @@ class _RankStep:
       (g_image,) = torch.autograd.grad(loss, image, allow_unused=True)
     if g_image is None:              # a loss that does not depend on this strip (empty strip): zeros join the collective
       g_image = torch.zeros_like(image)
-    return loss.detach(), g_image          # possibly an expanded scalar (sum / mean loss): see _image_grad_pointer
+    return loss.detach(), g_image          # possibly an expanded scalar (sum / mean loss): see frame.image_grad
 
-  def _image_grad_pointer(self, gr, g_image, moments_path, row_bytes_f):
-    """dL/dimage for the strip's raster backward.  A sum / mean loss hands autograd an EXPANDED scalar (strides 0): the
-    moments kernel then reads one pixel's values (``grad_image_broadcast``, as render_gaussians does) instead of an
-    (rows, W, f) copy that would be written here and read back there.  Returns the tensor that must stay alive."""
-    broadcast = (frame.BROADCAST_GRAD and moments_path and g_image.dim() == 3 and g_image.shape[0] * g_image.shape[1] > 1
-                 and g_image.stride(0) == 0 and g_image.stride(1) == 0)
-    if broadcast:
-      keep = g_image[0, 0].contiguous()
-      gr.grad_image, gr.grad_image_broadcast = keep.data_ptr(), 1
-    else:
-      keep = g_image.contiguous()
-      gr.grad_image, gr.grad_image_broadcast = keep.data_ptr() - row_bytes_f, 0
-    return keep
+  def _raster_backward_images(self, gr, image, g_image, moments_path, f):
+    """the strip image and dL/dimage of the strip's raster backward; returns the gradient tensor that must stay alive"""
+    gr.image = self.window.base(image, f, self._placeholder)
+    return frame.image_grad(gr, g_image, moments_path, self.window, f, self._placeholder)
 
   def check(self) -> dict:
     """Host read (synchronises the device) of the overflow indicators: the counters of the LAST step, and whether ANY
@@ -305,19 +278,16 @@ class StripStep(_RankStep):
     assert self.k_capacity > 0, "StripStep.probe() first (fixes the overlap-list capacity)"
     self._enter_step(gaussians, camera_params)
     lib = _lib.load()
-    tensors = [t.detach().contiguous() for t in (*gaussians.shape_tensors(), gaussians.feature,
-                                                 camera_params.T_camera_world.reshape(4, 4), camera_params.projection.reshape(4))]
-    pos, lsc, rot, alog, feat, Tcw, proj = tensors
+    tensors, inputs, f, degree = frame.gaussian_inputs(*gaussians.shape_tensors(), gaussians.feature,
+                                                       camera_params.T_camera_world.reshape(4, 4),
+                                                       camera_params.projection.reshape(4), use_sh)
+    pos, feat = tensors[0], tensors[4]
     device, dtype, n = pos.device, pos.dtype, pos.shape[0]
-    f, degree = _feature_shape(feat, use_sh)
     stream = _lib.current_stream(device)
     timer = self.timer
     timer.mark('start')
     desc, _ = frame.frame_desc(n, self.image_size, dtype, f, degree, self.config, self.depth_range, tile_rows=self.rows,
                                capacity=self.k_capacity)
-    inputs = _lib.FrameInputsC(position=pos.data_ptr(), log_scaling=lsc.data_ptr(), rotation=rot.data_ptr(),
-                               alpha_logit=alog.data_ptr(), feature=feat.data_ptr(), T_camera_world=Tcw.data_ptr(),
-                               projection=proj.data_ptr(), points7=None, depth=None, colours=None)
     lay, keep_n, keep_k, image, alpha = self._strip_forward(desc, inputs, device, dtype, f)
     timer.mark('project_sh_map_raster')
     loss, g_image = self._loss_and_image_grad(image, loss_fn, backward)
@@ -344,10 +314,7 @@ class StripStep(_RankStep):
     else:
       gp = torch.empty((n, 7), dtype=dtype, device=device) if moments_path else torch.zeros((n, 7), dtype=dtype, device=device)
       gc = torch.empty((n, f), dtype=dtype, device=device) if moments_path else torch.zeros((n, f), dtype=dtype, device=device)
-    y0 = self.px_rows[0]
-    row_bytes = y0 * self.image_size[0] * es
-    gr.image = image.data_ptr() - row_bytes * f
-    g_keep = self._image_grad_pointer(gr, g_image, moments_path, row_bytes * f)      # noqa: F841 (alive until the launch)
+    g_keep = self._raster_backward_images(gr, image, g_image, moments_path, f)      # noqa: F841 (alive until the launch)
     gr.stage = _lib.BACKWARD_RASTER
     if in_place:
       gr.grad_points7, gr.grad_colours, gr.boundary_stride = buf.data_ptr(), buf.data_ptr() + 7 * es, width
@@ -369,7 +336,6 @@ class StripStep(_RankStep):
     timer.mark('reduce_scatter_all_gather')
 
     need = [t.requires_grad for t in (*gaussians.shape_tensors(), gaussians.feature)]
-    grads = [torch.empty_like(t) if need[i] else None for i, t in enumerate((pos, lsc, rot, alog))]
     g2 = _lib.FrameGradsC()
     g2.stage = _lib.BACKWARD_GAUSSIANS
     g2.boundary_form = gr.boundary_form
@@ -377,14 +343,9 @@ class StripStep(_RankStep):
       g2.grad_points7, g2.grad_colours, g2.boundary_stride = buf.data_ptr(), buf.data_ptr() + 7 * es, width
     else:
       g2.grad_points7, g2.grad_colours = gp.data_ptr(), gc.data_ptr()
-    g2.grad_position, g2.grad_log_scaling, g2.grad_rotation, g2.grad_alpha_logit = (_lib.ptr(t) for t in grads)
-    grad_feature = None
-    if need[4]:
-      if degree >= 0:
-        grad_feature = torch.empty_like(feat)
-        g2.grad_feature = grad_feature.data_ptr()
-      else:
-        grad_feature = buf[:n, 7:].contiguous() if in_place else gc
+    grads, grad_feature = frame.gaussian_grads(g2, tensors, need, degree >= 0)
+    if need[4] and grad_feature is None:           # plain colours: the summed boundary gradient IS the feature gradient
+      grad_feature = buf[:n, 7:].contiguous() if in_place else gc
     _lib.check(lib.ms_frame_backward(ctypes.byref(desc), ctypes.byref(inputs), keep_n.data_ptr(), keep_k.data_ptr(),
                                      ctypes.byref(g2), stream), "strip step (gaussian backward)")
     timer.mark('gaussian_bwd')
@@ -452,12 +413,12 @@ class ShardedStep(_RankStep):
     assert self.k_capacity > 0 and self.bucket_capacity > 0, "ShardedStep.probe() first (fixes the capacities)"
     self._enter_step(shard, camera_params)
     lib = _lib.load()
-    tensors = [t.detach().contiguous() for t in (*shard.shape_tensors(), shard.feature,
-                                                 camera_params.T_camera_world.reshape(4, 4), camera_params.projection.reshape(4))]
-    pos, lsc, rot, alog, feat, Tcw, proj = tensors
+    tensors, in_a, f, degree = frame.gaussian_inputs(*shard.shape_tensors(), shard.feature,
+                                                     camera_params.T_camera_world.reshape(4, 4),
+                                                     camera_params.projection.reshape(4), use_sh)
+    pos, feat = tensors[0], tensors[4]
     device, dtype, n = pos.device, pos.dtype, pos.shape[0]
     assert dtype == torch.float32, "ShardedStep: float32 (the routing kernels of csrc/strip_route.hip)"
-    f, degree = _feature_shape(feat, use_sh)
     stream = _lib.current_stream(device)
     world, cap = self.world, self.bucket_capacity
     timer = self.timer
@@ -467,9 +428,6 @@ class ShardedStep(_RankStep):
     desc_a, _ = frame.frame_desc(n, self.image_size, dtype, f, degree, self.config, self.depth_range)
     lay_a = frame.frame_layout(desc_a)
     keep_a = frame.byte_block(lay_a.keep_n_bytes, device)
-    in_a = _lib.FrameInputsC(position=pos.data_ptr(), log_scaling=lsc.data_ptr(), rotation=rot.data_ptr(),
-                             alpha_logit=alog.data_ptr(), feature=feat.data_ptr(), T_camera_world=Tcw.data_ptr(),
-                             projection=proj.data_ptr(), points7=None, depth=None, colours=None)
     _lib.check(lib.ms_frame_project(ctypes.byref(desc_a), ctypes.byref(in_a), keep_a.data_ptr(), stream), "sharded step (project)")
     points7 = frame.block_view(keep_a, lay_a.points7, dtype, (n, 7))
     depth = frame.block_view(keep_a, lay_a.depth, dtype, (n,))
@@ -557,9 +515,7 @@ class ShardedStep(_RankStep):
     # ---- backward: strip raster -> gradients of the received rows -> home -> per-gaussian pass ---------------------
     gr = _lib.FrameGradsC()
     moments_path, det = self._raster_backward_mode(desc_b, gr, g_image, device, m)
-    row_bytes = self.px_rows[0] * self.image_size[0] * es
-    gr.image = image.data_ptr() - row_bytes * f
-    g_keep = self._image_grad_pointer(gr, g_image, moments_path, row_bytes * f)      # noqa: F841 (alive until the launch)
+    g_keep = self._raster_backward_images(gr, image, g_image, moments_path, f)      # noqa: F841 (alive until the launch)
     gr.stage = _lib.BACKWARD_RASTER
     bw = 7 + f
     if moments_path:
@@ -581,7 +537,6 @@ class ShardedStep(_RankStep):
     timer.mark('exchange_backward')
 
     need = [t.requires_grad for t in (*shard.shape_tensors(), shard.feature)]
-    grads = [torch.empty_like(t) if need[i] else None for i, t in enumerate((pos, lsc, rot, alog))]
     ga = _lib.FrameGradsC()
     ga.stage = _lib.BACKWARD_GAUSSIANS
     ga.boundary_form = gr.boundary_form
@@ -599,14 +554,9 @@ class ShardedStep(_RankStep):
                                             stream), "sharded step (return)")
       ga.grad_points7, ga.grad_colours = home.data_ptr(), home.data_ptr() + 7 * es
     ga.boundary_stride = bw
-    ga.grad_position, ga.grad_log_scaling, ga.grad_rotation, ga.grad_alpha_logit = (_lib.ptr(t) for t in grads)
-    grad_feature = None
-    if need[4]:
-      if degree >= 0:
-        grad_feature = torch.empty_like(feat)
-        ga.grad_feature = grad_feature.data_ptr()
-      else:
-        grad_feature = home[:, 7:].contiguous()
+    grads, grad_feature = frame.gaussian_grads(ga, tensors, need, degree >= 0)
+    if need[4] and grad_feature is None:           # plain colours: the rows summed at home hold the feature gradient
+      grad_feature = home[:, 7:].contiguous()
     _lib.check(lib.ms_frame_backward(ctypes.byref(desc_a), ctypes.byref(in_a), keep_a.data_ptr(), None,
                                      ctypes.byref(ga), stream), "sharded step (gaussian backward)")
     timer.mark('return_gaussian_bwd')

@@ -223,7 +223,7 @@ def test_deferred_visibility_bookkeeping_without_a_device():
   sums, never runs the pass on demand (no library call is made here: the early returns)."""
   assert frame.VISIBILITY_FROM_BACKWARD is False and frame.SH_SIDE_STREAM is True
   st = frame.FrameState()
-  assert (st.vis_deferred, st.vis_ready, st.vis_args, st.colours_ready) == (False, True, None, None)
+  assert (st.vis_deferred, st.vis_ready, st.vis_pass, st.colours_ready) == (False, True, None, None)
   passes = frame.visibility_passes
   st.ensure_visibility()                                       # not deferred
   st.vis_deferred, st.vis_ready = True, True

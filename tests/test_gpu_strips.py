@@ -51,22 +51,28 @@ def test_strips_compose_to_full_frame(world, dtype):
       ((got - want).abs().max(), scale)
 
 
-@pytest.mark.parametrize('features', [3, 6])
-def test_cropped_strip_equals_rows_of_full_frame(features):
+@pytest.mark.parametrize('features,heuristics,dtype', [
+  pytest.param(3, False, torch.float32, id='3'),                      # the moments path
+  pytest.param(6, False, torch.float32, id='6'),                      # channel chunks
+  pytest.param(2, False, torch.float32, id='2'),                      # the generic kernels, at most four channels
+  pytest.param(6, True, torch.float32, id='6-heuristics'),            # the zero-padded wide launch
+  pytest.param(3, False, torch.float64, id='3-float64')])             # the generic kernels
+def test_cropped_strip_equals_rows_of_full_frame(features, heuristics, dtype):
   # rasterize_with_tiles(..., tile_rows, crop_to_rows=True): only the strip's pixel rows are allocated
   from taichi_splatting_amd import rasterize_with_tiles, map_to_tiles
   from taichi_splatting_amd.misc.renderer2d import project_gaussians2d
   from taichi_splatting_amd.testing import random_2d_gaussians
   torch.manual_seed(features)
   size = (200, 150)            # 10 tile rows, the last one partial
-  cfg = RasterConfig()
-  g = random_2d_gaussians(5000, size, num_channels=features, scale_factor=1.5).to(DEV)
+  cfg = RasterConfig(compute_point_heuristic=heuristics)
+  g = random_2d_gaussians(5000, size, num_channels=features, scale_factor=1.5).to(device=DEV, dtype=dtype)
   p = project_gaussians2d(g)
   o2p, ranges = map_to_tiles(p, g.depths, size, cfg)
-  G = torch.randn(size[1], size[0], features, device=DEV)
+  G = torch.randn(size[1], size[0], features, device=DEV, dtype=dtype)
   pf = p.clone().requires_grad_(True); ff = g.feature.clone().requires_grad_(True)
   full = rasterize_with_tiles(pf, ff, o2p, ranges.view(-1, 2), size, cfg)
   gp_sum, gf_sum = torch.zeros_like(p), torch.zeros_like(g.feature)
+  heuristic_sum = torch.zeros_like(full.point_heuristic)
   for rows in ((0, 3), (3, 3), (3, 9), (9, 10)):
     ps = p.clone().requires_grad_(True); fs = g.feature.clone().requires_grad_(True)
     y0, y1 = rows[0] * 16, min(rows[1] * 16, size[1])
@@ -75,6 +81,10 @@ def test_cropped_strip_equals_rows_of_full_frame(features):
     assert torch.equal(out.image, full.image[y0:y1]) and torch.equal(out.image_weight, full.image_weight[y0:y1])
     (out.image * G[y0:y1]).sum().backward()
     gp_sum += ps.grad; gf_sum += fs.grad
+    heuristic_sum += out.point_heuristic              # (sums over the strip's pixels, filled by its backward pass)
   (full.image * G).sum().backward()
   assert torch.allclose(gp_sum, pf.grad, rtol=1e-4, atol=1e-4 * pf.grad.abs().max().item())
   assert torch.allclose(gf_sum, ff.grad, rtol=1e-4, atol=1e-5)
+  if heuristics:
+    assert full.point_heuristic.abs().max().item() > 0
+    assert torch.allclose(heuristic_sum, full.point_heuristic, rtol=1e-4, atol=1e-4 * full.point_heuristic.abs().max().item())
