@@ -124,20 +124,35 @@ __device__ __forceinline__ bool patch_hit(const CullBox<T>& b, T x0, T y0) {
 
 // ---- antialiased pdf, float: v_exp_f32 / v_rcp_f32 and the staged 1/sigma instead of expf and divisions
 // (generic.py:341-404; the double instantiation keeps the exact formulation of splat_math.h)
-__device__ __forceinline__ float aa_sigmoid(float x, float inv_sigma, float& z) {
-  z = x * inv_sigma;
-  // exp(-(1.6 z + 0.07 z^3)) = exp2(z (-1.6 log2e - 0.07 log2e z^2))
-  const float e = __builtin_amdgcn_exp2f(z * (-2.30831206544f - 0.100988652863f * z * z));
-  return __builtin_amdgcn_rcpf(1.0f + e);
+//
+// One cell edge: S(z) = 1 / (1 + exp(-h(z))), h = 1.6 z + 0.07 z^3, kept as t = exp(-|h|) in (0, 1] and r = 1 / (1 + t):
+// S = r for h >= 0, t r for h < 0, and S (1 - S) = t r^2.  The pdf needs S(hi) - S(lo) of a cell's two edges; in the tail
+// both S are 1 - O(threshold) and their rounded difference keeps ~1e-7 / (S(hi) - S(lo)) of relative accuracy only — 2e-2
+// at alpha_threshold 1e-4, enough to move a pair across the blend gate.  The difference is taken of the t instead.
+struct AaEdge { float z, t, r; bool pos; };
+
+__device__ __forceinline__ AaEdge aa_edge(float x, float inv_sigma) {
+  AaEdge e;
+  e.z = x * inv_sigma;
+  const float h2 = e.z * (2.30831206544f + 0.100988652863f * e.z * e.z);     // h(z) log2(e)
+  e.pos = h2 >= 0.0f;
+  e.t = __builtin_amdgcn_exp2f(-fabsf(h2));
+  e.r = __builtin_amdgcn_rcpf(1.0f + e.t);
+  return e;
+}
+
+// S(hi) - S(lo) for hi.z > lo.z (h is increasing: lo.pos implies hi.pos)
+__device__ __forceinline__ float aa_edge_diff(const AaEdge& hi, const AaEdge& lo) {
+  const float num = lo.pos ? lo.t - hi.t : (hi.pos ? 1.0f - hi.t * lo.t : hi.t - lo.t);
+  return num * hi.r * lo.r;
 }
 
 template <int F>
 __device__ __forceinline__ float aa_pdf(const Splat<float, F>& s, float px, float py) {
   const float dx = px - s.mx, dy = py - s.my;
   const float tx = dx * s.ax + dy * s.ay, ty = dy * s.ax - dx * s.ay;
-  float z;
-  const float ix = aa_sigmoid(tx + 0.5f, s.isx, z) - aa_sigmoid(tx - 0.5f, s.isx, z);
-  const float iy = aa_sigmoid(ty + 0.5f, s.isy, z) - aa_sigmoid(ty - 0.5f, s.isy, z);
+  const float ix = aa_edge_diff(aa_edge(tx + 0.5f, s.isx), aa_edge(tx - 0.5f, s.isx));
+  const float iy = aa_edge_diff(aa_edge(ty + 0.5f, s.isy), aa_edge(ty - 0.5f, s.isy));
   return 6.283185307179586f * (s.sx * ix) * (s.sy * iy);
 }
 
@@ -152,25 +167,26 @@ __device__ __forceinline__ float aa_pdf_with_grad(const Splat<float, F>& s, floa
                                                   float ga[2], float gs[2]) {
   const float dx = px - s.mx, dy = py - s.my;
   const float tx = dx * s.ax + dy * s.ay, ty = dy * s.ax - dx * s.ay;
-  // S, dS/dx and dS/dsigma at the four cell edges (generic.py:360-368)
-  float S[4], dS[4], dSs[4];
+  // dS/dx and dS/dsigma at the four cell edges (generic.py:360-368), S (1 - S) = t r^2
+  AaEdge e[4];
+  float dS[4], dSs[4];
   const float xs[4] = {tx + 0.5f, tx - 0.5f, ty + 0.5f, ty - 0.5f};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float inv = k < 2 ? s.isx : s.isy;
-    float z;
-    S[k] = aa_sigmoid(xs[k], inv, z);
-    const float d = (1.6f + 0.21f * z * z) * S[k] * (1.0f - S[k]);
+    e[k] = aa_edge(xs[k], inv);
+    const float d = (1.6f + 0.21f * e[k].z * e[k].z) * (e[k].t * e[k].r * e[k].r);
     dS[k] = d * inv;
-    dSs[k] = -dS[k] * z;
+    dSs[k] = -dS[k] * e[k].z;
   }
   const float tau = 6.283185307179586f;
-  const float ix = s.sx * (S[0] - S[1]), iy = s.sy * (S[2] - S[3]);
+  const float Dx = aa_edge_diff(e[0], e[1]), Dy = aa_edge_diff(e[2], e[3]);
+  const float ix = s.sx * Dx, iy = s.sy * Dy;
   const float dSx = iy * s.sx * (dS[0] - dS[1]), dSy = ix * s.sy * (dS[2] - dS[3]);
   gm[0] = tau * (dSy * s.ay - dSx * s.ax);
   gm[1] = -tau * (dSx * s.ay + dSy * s.ax);
-  gs[0] = tau * iy * (S[0] - S[1] + (dSs[0] - dSs[1]) * s.sx);
-  gs[1] = tau * ix * (S[2] - S[3] + (dSs[2] - dSs[3]) * s.sy);
+  gs[0] = tau * iy * (Dx + (dSs[0] - dSs[1]) * s.sx);
+  gs[1] = tau * ix * (Dy + (dSs[2] - dSs[3]) * s.sy);
   ga[0] = tau * (dSx * dx + dSy * dy);
   ga[1] = tau * (dSx * dy - dSy * dx);
   return tau * ix * iy;

@@ -12,10 +12,10 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
 
-def make_scene(n, size, seed, sh_degree=None, dtype=torch.float64):
+def make_scene(n, size, seed, sh_degree=None, dtype=torch.float64, margin=0.1, alpha_range=(0.1, 0.9)):
   torch.manual_seed(seed)
   cam = random_camera(image_size=size)
-  g = random_3d_gaussians(n, cam, scale_factor=1.0, alpha_range=(0.1, 0.9), margin=0.1)
+  g = random_3d_gaussians(n, cam, scale_factor=1.0, alpha_range=alpha_range, margin=margin)
   if sh_degree is not None:
     g = g.replace(feature=(torch.rand(n, 3, (sh_degree + 1) ** 2) - 0.5) * 0.5)
   return g.to(dtype=dtype), cam.to(dtype=dtype)

@@ -35,10 +35,11 @@ def cfg_for(tile, **kw):
 
 
 def confined_scene(per_tile, size, tile, seed, alpha_range=(0.01, 0.03), sigma=(0.5, 0.4), inset=4.0, pool=1.5,
-                   exact=False):
+                   exact=False, cfg=None):
   """``per_tile`` gate-stable splats per tile with their centres ``inset`` px inside the tile.  A pool of
   ``pool * per_tile`` candidates per tile is drawn, the candidates with a (pixel, splat) pair within 1e-4 of the blend
-  gate are dropped (the margin of a pair does not depend on the other splats), the first ``per_tile`` of each tile kept."""
+  gate are dropped (the margin of a pair does not depend on the other splats), the first ``per_tile`` of each tile kept.
+  ``cfg``: the config whose blend gate (alpha_threshold) the margin is measured at; the default one of the tile size if None."""
   tw, th = (size[0] + tile - 1) // tile, (size[1] + tile - 1) // tile
   tiles = tw * th
   n = int(per_tile * pool) * tiles
@@ -48,7 +49,8 @@ def confined_scene(per_tile, size, tile, seed, alpha_range=(0.01, 0.03), sigma=(
   span = tile - 2 * inset
   g.position[:] = torch.stack([(owner % tw) * tile + inset + span * torch.rand(n), (owner // tw) * tile + inset + span * torch.rand(n)], 1)
   g.log_scaling[:] = torch.log(sigma[0] + sigma[1] * torch.rand(n, 2))
-  cfg = cfg_for(tile)
+  cfg = cfg_for(tile) if cfg is None else cfg
+  assert cfg.tile_size == tile
   p = project_gaussians2d(g)
   o2p, ranges = map_to_tiles(p.to(DEV), g.depths.reshape(-1, 1).to(DEV), size, cfg)
   margin = orast.gate_margin(p.double(), ranges.cpu(), o2p.cpu(), size, cfg)
@@ -81,19 +83,37 @@ def oracle_pair(p, f, ranges, o2p, size, cfg, G):
   return img, alpha, vis, gp, gf, heur
 
 
-def report_rows(what, got, want, p, ranges, o2p, size, cfg, tol=TOL):
+def report_rows(what, got, want, p, ranges, o2p, size, cfg, tol=TOL, flagged=None, interval=None):
   """Every row within ``tol`` of the largest gradient; the rows beyond 2e-5 are LISTED with the side of the saturation
-  test their nearest pair sits on and its distance to it (gate_excess style: printed and appended to the parity log)."""
+  test their nearest pair sits on and its distance to it (gate_excess style: printed and appended to the parity log).
+
+  ``flagged`` (rows,) bool with ``interval`` = (lo, hi): rows that have a pair on the saturation limit itself
+  (tests/threshold_cases.py).  Their error is the distance, element by element, to the interval [lo, hi] instead of the
+  distance to ``want``; it is held to the same ``tol``, and every one of them is listed."""
   want = want.double().cpu()
   scale = float(want.abs().max())
   assert scale > 0
-  rel = ((got.detach().cpu().double() - want).abs() / scale).reshape(want.shape[0], -1).max(dim=1).values
+  got64 = got.detach().cpu().double()
+  err = (got64 - want).abs()
+  listed = None
+  if flagged is not None:
+    lo, hi = interval
+    outside = torch.clamp_min(lo - got64, 0) + torch.clamp_min(got64 - hi, 0)
+    err = torch.where(flagged.reshape([-1] + [1] * (err.dim() - 1)), outside, err)
+    listed = flagged
+  rel = (err / scale).reshape(want.shape[0], -1).max(dim=1).values
   over = torch.nonzero(rel > 2e-5).squeeze(1)
   entry = {"what": what, "kind": "rows vs oracle", "rows": int(rel.numel()), "beyond_2e-5": int(over.numel()), "largest": float(rel.max())}
+  if listed is not None:
+    entry["flagged"] = int(listed.sum())
+    over = torch.nonzero((rel > 2e-5) | listed).squeeze(1)
+    order = torch.argsort(~listed[over], stable=True)          # the flagged rows first: all of them are listed
+    over = over[order][:max(32, int(listed.sum()))]
   if over.numel():
     margin, side = orast.saturation_margin(p.cpu().double(), ranges.cpu(), o2p.cpu(), size, cfg)
     entry["beyond_2e-5_rows"] = [{"row": int(i), "rel": float(rel[i]), "saturation_side": int(side[i]),
-                                  "saturation_margin": float(margin[i])} for i in over[:32]]
+                                  "saturation_margin": float(margin[i]),
+                                  **({"flagged": bool(listed[i])} if listed is not None else {})} for i in over[:32 if listed is None else None]]
   print('parity rows:', json.dumps(entry))
   try:
     from oracle.gate_excess import _record
@@ -271,6 +291,30 @@ def test_frame_executor_segments_vs_oracle():
   report_rows("frame executor segments, d features", fg.grad, gf_o, p, ranges, o2p, size, cfg)
 
 
+def splat_rows_forward(lib, p, depth, f, o2p, ranges, size, cfg):
+  """ms_splat_rows_pack + ms_raster_fwd_rows through the C-ABI: (rows, image, alpha, visibility)"""
+  n, (w, h), tile = p.shape[0], size, cfg.tile_size
+  cfg_c, stream = _lib.raster_config_c(cfg), _lib.current_stream(torch.device(DEV))
+  th = (h + tile - 1) // tile
+  rows = torch.full((n, _lib.SPLAT_ROW), float('nan'), device=DEV)
+  _lib.check(lib.ms_splat_rows_pack(p.data_ptr(), depth.data_ptr(), f.data_ptr(), n, rows.data_ptr(), stream), "pack")
+  image, alpha, vis = torch.empty((h, w, 3), device=DEV), torch.empty((h, w), device=DEV), torch.zeros(n, device=DEV)
+  _lib.check(lib.ms_raster_fwd_rows(rows.data_ptr(), ranges.data_ptr(), o2p.data_ptr(), w, h, cfg_c, image.data_ptr(),
+                                    alpha.data_ptr(), vis.data_ptr(), 0, th, stream), "fwd rows")
+  return rows, image, alpha, vis
+
+
+def splat_rows_backward(lib, rows, o2p, ranges, image, G, size, cfg):
+  """ms_raster_bwd_moments_rows through the C-ABI: (return code, moments)"""
+  n, (w, h), tile = rows.shape[0], size, cfg.tile_size
+  cfg_c, stream = _lib.raster_config_c(cfg), _lib.current_stream(torch.device(DEV))
+  th = (h + tile - 1) // tile
+  mom = torch.zeros((n, _lib.MOMENT_ROW), device=DEV)
+  rc = lib.ms_raster_bwd_moments_rows(rows.data_ptr(), ranges.data_ptr(), o2p.data_ptr(), image.data_ptr(), G.data_ptr(), w, h,
+                                      cfg_c, mom.data_ptr(), 0, None, 0, th, stream)
+  return rc, mom
+
+
 @pytest.mark.parametrize('tile,heuristics', [(16, False), (16, True), (32, False), (8, False)])
 def test_splat_row_entry_points_vs_oracle(tile, heuristics):
   """ms_splat_rows_pack -> ms_raster_fwd_rows -> ms_raster_bwd_moments_rows (one 64-byte row per splat gathered instead
@@ -287,29 +331,21 @@ def test_splat_row_entry_points_vs_oracle(tile, heuristics):
   assert float(keep.float().mean()) > 0.7
   g = g0[keep]
   p, f, o2p, ranges = lists_for(g, size, cfg)
-  n, (w, h) = p.shape[0], size
+  (w, h) = size
   depth = g.depths.reshape(-1).to(DEV).contiguous()
-  cfg_c, stream = _lib.raster_config_c(cfg), _lib.current_stream(torch.device(DEV))
-  th = (h + tile - 1) // tile
-  rows = torch.full((n, _lib.SPLAT_ROW), float('nan'), device=DEV)
-  _lib.check(lib.ms_splat_rows_pack(p.data_ptr(), depth.data_ptr(), f.data_ptr(), n, rows.data_ptr(), stream), "pack")
-  image, alpha, vis = torch.empty((h, w, 3), device=DEV), torch.empty((h, w), device=DEV), torch.zeros(n, device=DEV)
-  _lib.check(lib.ms_raster_fwd_rows(rows.data_ptr(), ranges.data_ptr(), o2p.data_ptr(), w, h, cfg_c, image.data_ptr(),
-                                    alpha.data_ptr(), vis.data_ptr(), 0, th, stream), "fwd rows")
+  rows, image, alpha, vis = splat_rows_forward(lib, p, depth, f, o2p, ranges, size, cfg)
   torch.manual_seed(1)
   G = (torch.rand(h, w, 3, device=DEV) + 0.5).contiguous()
   img_o, a_o, vis_o, gp_o, gf_o, heur_o = oracle_pair(p, f, ranges, o2p, size, cfg, G)
   assert (image.cpu().double() - img_o).abs().max().item() < TOL
   assert (alpha.cpu().double() - a_o).abs().max().item() < TOL
   assert (vis.cpu().double() - vis_o).abs().max().item() < TOL * float(vis_o.max())
-  mom = torch.zeros((n, _lib.MOMENT_ROW), device=DEV)
-  rc = lib.ms_raster_bwd_moments_rows(rows.data_ptr(), ranges.data_ptr(), o2p.data_ptr(), image.data_ptr(), G.data_ptr(), w, h,
-                                      cfg_c, mom.data_ptr(), 0, None, 0, th, stream)
+  rc, mom = splat_rows_backward(lib, rows, o2p, ranges, image, G, size, cfg)
   if tile == 8:
     assert rc == -2                                                     # MS_ERR_UNSUPPORTED (measured slower: not offered)
     return
   _lib.check(rc, "bwd rows")
-  gp, gf, heur = finalize(lib, p, mom, heuristics, stream)
+  gp, gf, heur = finalize(lib, p, mom, heuristics, _lib.current_stream(torch.device(DEV)))
   what = f"splat rows tile {tile}"
   report_rows(what + " d gaussians2d", gp, gp_o, p, ranges, o2p, size, cfg)
   report_rows(what + " d features", gf, gf_o, p, ranges, o2p, size, cfg)

@@ -58,13 +58,17 @@ def test_strips_compose_to_full_frame(world, dtype):
   pytest.param(6, True, torch.float32, id='6-heuristics'),            # the zero-padded wide launch
   pytest.param(3, False, torch.float64, id='3-float64')])             # the generic kernels
 def test_cropped_strip_equals_rows_of_full_frame(features, heuristics, dtype):
+  check_cropped_strips(features, dtype, RasterConfig(compute_point_heuristic=heuristics))
+
+
+def check_cropped_strips(features, dtype, cfg):
   # rasterize_with_tiles(..., tile_rows, crop_to_rows=True): only the strip's pixel rows are allocated
   from taichi_splatting_amd import rasterize_with_tiles, map_to_tiles
   from taichi_splatting_amd.misc.renderer2d import project_gaussians2d
   from taichi_splatting_amd.testing import random_2d_gaussians
   torch.manual_seed(features)
   size = (200, 150)            # 10 tile rows, the last one partial
-  cfg = RasterConfig(compute_point_heuristic=heuristics)
+  heuristics = cfg.compute_point_heuristic
   g = random_2d_gaussians(5000, size, num_channels=features, scale_factor=1.5).to(device=DEV, dtype=dtype)
   p = project_gaussians2d(g)
   o2p, ranges = map_to_tiles(p, g.depths, size, cfg)
@@ -88,3 +92,4 @@ def test_cropped_strip_equals_rows_of_full_frame(features, heuristics, dtype):
   if heuristics:
     assert full.point_heuristic.abs().max().item() > 0
     assert torch.allclose(heuristic_sum, full.point_heuristic, rtol=1e-4, atol=1e-4 * full.point_heuristic.abs().max().item())
+  return p, g.feature, g.depths, size
