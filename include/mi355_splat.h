@@ -104,6 +104,14 @@ int ms_sh_fwd(const void* params, const void* positions, const int64_t* indexes,
               const void* camera_pos, int64_t v, int f, int degree, void* out,
               int dtype, void* stream);
 
+/* ms_sh_fwd at an ACTIVE degree (the SH band schedule of a trainer, a diffuse-only view): params is stored at `degree`,
+ * (M, F, (degree+1)^2), and only its first (active_degree+1)^2 coefficients per channel are evaluated, in place — the
+ * colours of the sliced tensor params[:, :, :(active_degree+1)^2].  0 <= active_degree <= degree;
+ * ms_sh_fwd(.., degree, ..) is ms_sh_fwd_active(.., degree, degree, ..). */
+int ms_sh_fwd_active(const void* params, const void* positions, const int64_t* indexes,
+                     const void* camera_pos, int64_t v, int f, int degree, int active_degree, void* out,
+                     int dtype, void* stream);
+
 /* evaluate_sh_at_kernel.grad (indexed_spherical_harmonics.py:153-160).  grad_params (M,F,D),
  * grad_positions (M,3) and grad_camera_pos (3) are ACCUMULATED atomically (indexes may repeat);
  * any of them may be NULL.  out = the saved forward output (V,F) or NULL: with it, and when only
@@ -115,6 +123,15 @@ int ms_sh_bwd(const void* params, const void* positions, const int64_t* indexes,
               const void* camera_pos, int64_t v, int f, int degree, const void* out,
               const void* grad_out, void* grad_params, void* grad_positions,
               void* grad_camera_pos, int unique_indexes, int dtype, void* stream);
+
+/* ms_sh_bwd at an active degree: grad_params keeps the stored shape (M, F, (degree+1)^2); the gradient of the inactive
+ * coefficients is exactly zero — written as zeros wherever whole rows are written (`out` given, f <= 4,
+ * unique_indexes), left at the caller's zeros where rows are accumulated — and grad_positions / grad_camera_pos see
+ * the active bands only.  ms_sh_bwd(.., degree, ..) is ms_sh_bwd_active(.., degree, degree, ..). */
+int ms_sh_bwd_active(const void* params, const void* positions, const int64_t* indexes,
+                     const void* camera_pos, int64_t v, int f, int degree, int active_degree, const void* out,
+                     const void* grad_out, void* grad_params, void* grad_positions,
+                     void* grad_camera_pos, int unique_indexes, int dtype, void* stream);
 
 /* ---- tile mapper -----------------------------------------------------------------------------
  * ms_tile_count replaces tile_overlaps_kernel (mapper/tile_mapper.py:76-86): counts[j] = number
@@ -375,6 +392,10 @@ typedef struct ms_frame_desc {
                                       launches when there is no such run: set it for scene shapes that showed one
                                       (ms_frame_inputs.longest_run_host) */
   int32_t split_seg_len;           /* 0: the default segment length; else ms_raster_fwd_split's split_seg_len */
+  int32_t sh_active_bands;         /* 0: every stored SH band; 1 .. sh_degree + 1: only that many bands (active degree + 1)
+                                      are evaluated and differentiated — colours of `feature` sliced to them, the
+                                      gradient of the other coefficients written as zeros (ms_sh_fwd_active); the same
+                                      in every call of a frame.  Refused above sh_degree + 1 and without SH */
   double near_plane, far_plane, blur_cov, clamp_margin;
   ms_raster_config raster;
 } ms_frame_desc;

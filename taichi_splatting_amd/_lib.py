@@ -68,6 +68,7 @@ class FrameDescC(_SizedStructure):
     ('dtype', c_int32), ('f', c_int32), ('sh_degree', c_int32), ('depth16', c_int32),
     ('tile_row_begin', c_int32), ('tile_row_end', c_int32),
     ('projected_input', c_int32), ('mapper', c_int32), ('split_long_runs', c_int32), ('split_seg_len', c_int32),
+    ('sh_active_bands', c_int32),
     ('near_plane', c_double), ('far_plane', c_double), ('blur_cov', c_double), ('clamp_margin', c_double),
     ('raster', RasterConfigC),
   ]
@@ -137,6 +138,8 @@ SIGNATURES = {
   'ms_project_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_double, c_double, c_void_p, c_int64] + [c_void_p] * 7 + [c_int, c_void_p]),
   'ms_sh_fwd': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),
   'ms_sh_bwd': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),
+  'ms_sh_fwd_active': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+  'ms_sh_bwd_active': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),
   'ms_tile_count': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]),
   'ms_depth_sort_keys': (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_void_p, c_void_p, c_int, c_void_p]),
   'ms_depth_argsort': (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),

@@ -59,6 +59,10 @@ static int check_desc(const ms_frame_desc* d, const char* who) {
   if (ts != 8 && ts != 16 && ts != 32) { set_error("%s: tile_size must be 8, 16 or 32 (got %d)", who, ts); return MS_ERR_UNSUPPORTED; }
   if (d->f < 1 || d->f > 4) { set_error("%s: 1..4 colour channels (got %d)", who, d->f); return MS_ERR_UNSUPPORTED; }
   if (d->sh_degree < -1 || d->sh_degree > 3) { set_error("%s: SH degree must be in [0, 3]", who); return MS_ERR_BAD_ARG; }
+  if (d->sh_active_bands < 0 || d->sh_active_bands > d->sh_degree + 1) {
+    set_error("%s: sh_active_bands must be 0 (all) or 1 .. sh_degree + 1 (got %d with sh_degree %d)", who, d->sh_active_bands, d->sh_degree);
+    return MS_ERR_BAD_ARG;
+  }
   if (d->mapper != MS_MAPPER_DIRECT && d->mapper != MS_MAPPER_PRESORT) { set_error("%s: mapper must be MS_MAPPER_DIRECT or MS_MAPPER_PRESORT (got %d)", who, d->mapper); return MS_ERR_BAD_ARG; }
   if (d->projected_input && d->sh_degree >= 0) { set_error("%s: projected input carries colours, not SH", who); return MS_ERR_BAD_ARG; }
   if (d->depth16) {
@@ -248,7 +252,8 @@ static int frame_project_impl(const ms_frame_desc* desc, const ms_frame_inputs* 
   }
   if (colours && d.sh_degree >= 0)
     MS_TRY(sh_fwd_inplace_launch(in->feature, in->position, kn + L.depth, kn + L.camera_position, d.n, d.f,
-                                 d.sh_degree, kn + L.colours, d.dtype, (hipStream_t)stream, rows));
+                                 d.sh_degree, d.sh_active_bands > 0 ? d.sh_active_bands - 1 : d.sh_degree, kn + L.colours,
+                                 d.dtype, (hipStream_t)stream, rows));
   return 0;
 }
 
@@ -506,7 +511,7 @@ extern "C" int ms_frame_backward(const ms_frame_desc* desc, const ms_frame_input
     }
   }
   a.extra_points7 = gr->extra_points7; a.extra_depth = gr->extra_depth; a.extra_colours = gr->extra_colours;
-  a.sh_degree = d.sh_degree; a.f = d.f;
+  a.sh_degree = d.sh_degree; a.f = d.f; a.sh_active_bands = d.sh_active_bands;
   a.camera_position = kn + L.camera_position; a.colours = colours;
   a.grad_position = gr->grad_position; a.grad_log_scaling = gr->grad_log_scaling; a.grad_rotation = gr->grad_rotation;
   a.grad_alpha_logit = gr->grad_alpha_logit; a.grad_feature = gr->grad_feature; a.grad_camera = gr->grad_camera;

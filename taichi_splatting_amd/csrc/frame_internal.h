@@ -111,7 +111,8 @@ int project_fwd_launch(const void* position, const void* log_scaling, const void
 // their 4 F D parameter bytes are not read
 // splat_rows (float32 RGB only): the colours also go into words 8..10 of each gaussian's splat row (raster_common.h)
 int sh_fwd_inplace_launch(const void* params, const void* positions, const void* depth, const void* cam_pos,
-                          int64_t n, int f, int degree, void* out, int dtype, hipStream_t s, float* splat_rows = nullptr);
+                          int64_t n, int f, int degree, int active_degree, void* out, int dtype, hipStream_t s,
+                          float* splat_rows = nullptr);
 
 // ---- raster.hip -------------------------------------------------------------------------------------------------
 // Splat rows (raster_common.h: SPLAT_ROW floats per gaussian, [points7 | depth | colour | 0]): a side table the frame
@@ -164,6 +165,7 @@ struct GaussianBwdArgs {
   const void *extra_points7, *extra_depth, *extra_colours;
   // SH (degree >= 0): d(colour) -> d(sh params) through the clamp mask of the forward colours
   int sh_degree, f;
+  int sh_active_bands;       // 0: every stored band; 1 .. sh_degree + 1: that many (ms_frame_desc.sh_active_bands)
   const void *camera_position, *colours;
   // outputs (each may be NULL)
   void *grad_position, *grad_log_scaling, *grad_rotation, *grad_alpha_logit;

@@ -50,11 +50,16 @@ template <typename T> struct GaussBwdDev {
 // MOM: the 2D-boundary gradients come from the moment rows (float32, RGB); FIXED: rows of 64-bit fixed point.
 // DEG >= 0: d(colour) -> d(SH parameters); DEG == -1: plain colours (grad_feature (n, 3) from the moment rows only —
 // with gradient arrays the caller already holds d(colour)).
-template <typename T, int DEG, bool MOM, bool FIXED>
-__global__ void __launch_bounds__(256)
-gaussian_bwd_kernel(const GaussBwdDev<T> a) {
+// STRIDED: DEG is the ACTIVE degree of a scene stored at a higher one (ms_frame_desc.sh_active_bands, sh.hip), whose
+// stored_d = (stored degree + 1)^2 coefficients per channel arrive at run time: the LDS rows hold the basis padded with
+// zeros to 16 values at the degree-3 stride, and the SH tail writes whole rows of stored_d coefficients, the inactive
+// ones as zeros.  STRIDED = false is the code of the kernels that evaluate every stored band, with constant strides.
+template <typename T, int DEG, bool MOM, bool FIXED, bool STRIDED>
+__device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int stored_d) {
   constexpr int D = DEG >= 0 ? (DEG + 1) * (DEG + 1) : 1;
-  constexpr int YS = D + 1;                      // padded row stride: conflict-free per-lane writes
+  constexpr int YW = STRIDED ? 16 : D;           // basis values per LDS row (zeros behind the active ones)
+  constexpr int YS = YW + 1;                     // padded row stride: conflict-free per-lane writes
+  const int SD = STRIDED ? stored_d : D;         // coefficients per (gaussian, channel) in memory
   __shared__ T s_Y[DEG >= 0 ? 4 : 1][DEG >= 0 ? 64 * YS : 1];
   __shared__ T s_g[DEG >= 0 ? 4 : 1][DEG >= 0 ? 64 * GB_MAX_F : 1];
   __shared__ T s_cam[4 * 16];
@@ -69,11 +74,22 @@ gaussian_bwd_kernel(const GaussBwdDev<T> a) {
   for (int k = 0; k < 16; ++k) cam_grad[k] = T(0);
 
   Camera<T> cam;
+  ProjParams<T> pp = a.pp;
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) cam.t[i][j] = a.Tcw[i * 4 + j];
   cam.fx = a.proj[0]; cam.fy = a.proj[1]; cam.cx = a.proj[2]; cam.cy = a.proj[3];
+  if constexpr (STRIDED && !MOM && sizeof(T) == 4) {
+    // the gradient-array form reads the most pointers of GaussBwdDev: with the camera in scalar registers as well the
+    // compiler runs out of them and reserves spill slots (a private segment).  Vector registers are not short here.
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(cam.t[i][j]));
+    asm volatile("" : "+v"(cam.fx), "+v"(cam.fy), "+v"(cam.cx), "+v"(cam.cy));
+    asm volatile("" : "+v"(pp.width), "+v"(pp.height), "+v"(pp.blur_cov), "+v"(pp.clamp_margin), "+v"(pp.alpha_threshold));
+  }
 
   // a wave takes 64 consecutive gaussians per iteration (the SH rows of a wave leave as coalesced stores)
   for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * 64; base < a.n; base += (int64_t)gridDim.x * 256) {
@@ -116,7 +132,7 @@ gaussian_bwd_kernel(const GaussBwdDev<T> a) {
       const T ls[3] = {a.log_scaling[i * 3 + 0], a.log_scaling[i * 3 + 1], a.log_scaling[i * 3 + 2]};
       const T q[4] = {a.rotation[i * 4 + 0], a.rotation[i * 4 + 1], a.rotation[i * 4 + 2], a.rotation[i * 4 + 3]};
       ProjState<T> st;
-      project_forward(p, ls, q, a.alpha_logit[i], cam, a.pp, st);
+      project_forward(p, ls, q, a.alpha_logit[i], cam, pp, st);
 
       if constexpr (MOM) {
         // moments -> gradients of the packed 2D gaussian and its colour (raster_bwd_scan.hip, generic.py:321-336);
@@ -205,10 +221,12 @@ gaussian_bwd_kernel(const GaussBwdDev<T> a) {
       if constexpr (DEG >= 0) {
         const T dx = p[0] - a.camera_position[0], dy = p[1] - a.camera_position[1], dz = p[2] - a.camera_position[2];
         const T len = t_sqrt(dx * dx + dy * dy + dz * dz);
-        T Y[D];
+        T Y[YW];
+#pragma unroll
+        for (int d = D; d < YW; ++d) Y[d] = T(0);
         sh_basis<T, DEG>(dx / len, dy / len, dz / len, Y);
 #pragma unroll
-        for (int d = 0; d < D; ++d) s_Y[wave][lane * YS + d] = Y[d];
+        for (int d = 0; d < YW; ++d) s_Y[wave][lane * YS + d] = Y[d];
         // the clamp passes the gradient strictly inside (0, 1) (sh.hip)
         _Pragma("unroll") for (int c = 0; c < GB_MAX_F; ++c) if (c < a.f) {
           const T o = a.colours[i * a.f + c];
@@ -218,7 +236,7 @@ gaussian_bwd_kernel(const GaussBwdDev<T> a) {
     } else if (valid) {
       if constexpr (DEG >= 0) {
 #pragma unroll
-        for (int d = 0; d < D; ++d) s_Y[wave][lane * YS + d] = T(0);
+        for (int d = 0; d < YW; ++d) s_Y[wave][lane * YS + d] = T(0);
         _Pragma("unroll") for (int c = 0; c < GB_MAX_F; ++c) if (c < a.f) s_g[wave][lane * GB_MAX_F + c] = T(0);
       }
     }
@@ -258,14 +276,14 @@ gaussian_bwd_kernel(const GaussBwdDev<T> a) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int row = a.f * D;
+        const int row = a.f * SD;
         T* dst0 = a.grad_feature + base * row;
-        if (D % 4 == 0 && a.f == 3 && sizeof(T) == 4 && (reinterpret_cast<uintptr_t>(a.grad_feature) & 15) == 0) {
+        if (SD % 4 == 0 && a.f == 3 && sizeof(T) == 4 && (reinterpret_cast<uintptr_t>(a.grad_feature) & 15) == 0) {
           // RGB, degree 1 / 3, float: the wave's 64 x 3 x D values leave as 128-bit stores of consecutive addresses
-          constexpr int PIECES = 3 * D / 4;
+          const int PIECES = 3 * SD / 4;
           for (int qi = lane; qi < count * PIECES; qi += 64) {
             const int j = qi / PIECES, k = qi - j * PIECES;
-            const int c = (4 * k) / D, d0 = 4 * k - c * D;
+            const int c = (4 * k) / SD, d0 = 4 * k - c * SD;
             const T g = s_g[wave][j * GB_MAX_F + c];
             const T* y = &s_Y[wave][j * YS + d0];
             typedef float vec4 __attribute__((ext_vector_type(4)));
@@ -275,7 +293,7 @@ gaussian_bwd_kernel(const GaussBwdDev<T> a) {
         } else {
           for (int e = lane; e < count * row; e += 64) {
             const int j = e / row, r = e - j * row;
-            dst0[e] = s_g[wave][j * GB_MAX_F + r / D] * s_Y[wave][j * YS + r % D];
+            dst0[e] = s_g[wave][j * GB_MAX_F + r / SD] * s_Y[wave][j * YS + r % SD];
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -286,6 +304,18 @@ gaussian_bwd_kernel(const GaussBwdDev<T> a) {
   }
 
   if (a.grad_camera) block_sum_commit<T, 16>(cam_grad, a.grad_camera, s_cam);
+}
+
+template <typename T, int DEG, bool MOM, bool FIXED>
+__global__ void __launch_bounds__(256)
+gaussian_bwd_kernel(const GaussBwdDev<T> a) {
+  gaussian_bwd_body<T, DEG, MOM, FIXED, false>(a, 0);
+}
+
+template <typename T, int DEG, bool MOM, bool FIXED>      // DEG: the active degree, below the stored one
+__global__ void __launch_bounds__(256)
+gaussian_bwd_active_kernel(const GaussBwdDev<T> a, int stored_d) {
+  gaussian_bwd_body<T, DEG, MOM, FIXED, true>(a, stored_d);
 }
 
 template <typename T>
@@ -317,9 +347,19 @@ static int launch_typed(const GaussianBwdArgs& g, hipStream_t s) {
   if (g.grad_camera && blocks > 2048) blocks = 2048;      // bounded atomic count for the 16 camera sums
   const dim3 grid((unsigned)blocks), block(256);
   const bool mom = g.moments != nullptr;
+  // fewer active bands than stored ones: the *_active_kernel of the active degree, the stored row length at run time
+  const int active = g.sh_active_bands > 0 && g.sh_active_bands <= g.sh_degree ? g.sh_active_bands - 1 : g.sh_degree;
+  const int stored_d = (g.sh_degree + 1) * (g.sh_degree + 1);
 #define MS_GO(DEG, MOM, FIXED) gaussian_bwd_kernel<T, DEG, MOM, FIXED><<<grid, block, 0, s>>>(a)
+#define MS_GO_A(DEG, MOM, FIXED) gaussian_bwd_active_kernel<T, DEG, MOM, FIXED><<<grid, block, 0, s>>>(a, stored_d)
 #define MS_GO_DEG(MOM, FIXED)                                        \
-  switch (g.sh_degree) {                                             \
+  if (active < g.sh_degree) {                                        \
+    switch (active) {                                                \
+      case 0: MS_GO_A(0, MOM, FIXED); break;                         \
+      case 1: MS_GO_A(1, MOM, FIXED); break;                         \
+      default: MS_GO_A(2, MOM, FIXED); break;                        \
+    }                                                                \
+  } else switch (g.sh_degree) {                                      \
     case -1: MS_GO(-1, MOM, FIXED); break;                           \
     case 0: MS_GO(0, MOM, FIXED); break;                             \
     case 1: MS_GO(1, MOM, FIXED); break;                             \
@@ -334,6 +374,7 @@ static int launch_typed(const GaussianBwdArgs& g, hipStream_t s) {
     MS_GO_DEG(false, false)
   }
 #undef MS_GO_DEG
+#undef MS_GO_A
 #undef MS_GO
   return 0;
 }
@@ -343,6 +384,7 @@ int gaussian_bwd_launch(const GaussianBwdArgs& g, hipStream_t s) {
   if (g.dtype != MS_F32 && g.dtype != MS_F64) { set_error("gaussian backward: dtype must be MS_F32 or MS_F64"); return MS_ERR_BAD_ARG; }
   if (g.sh_degree < -1 || g.sh_degree > 3) { set_error("gaussian backward: SH degree must be in [0, 3]"); return MS_ERR_BAD_ARG; }
   if (g.moments && (g.dtype != MS_F32 || g.f != 3)) { set_error("gaussian backward: moment rows are float32 RGB"); return MS_ERR_BAD_ARG; }
+  if (g.sh_active_bands < 0 || g.sh_active_bands > g.sh_degree + 1) { set_error("gaussian backward: more active SH bands than stored ones"); return MS_ERR_BAD_ARG; }
   if (g.sh_degree >= 0 && (g.f < 1 || g.f > GB_MAX_F)) { set_error("gaussian backward: 1..4 SH colour channels"); return MS_ERR_UNSUPPORTED; }
   if (!g.position || !g.log_scaling || !g.rotation || !g.alpha_logit || !g.T_camera_world || !g.projection || !g.depth) {
     set_error("gaussian backward: null input"); return MS_ERR_BAD_ARG;

@@ -118,6 +118,7 @@ class FrameOptions:
   tile_rows: Optional[Tuple[int, int]] = None
   crop_to_rows: bool = False
   render_median_depth: bool = False
+  sh_degree: Optional[int] = None       # active SH degree (render_gaussians(sh_degree=...)); None: every stored band
 
 
 def frame_supported(feature: torch.Tensor, config: RasterConfig, use_sh: bool) -> bool:
@@ -396,12 +397,15 @@ def byte_block(nbytes, device):
 
 
 def frame_desc(n, image_size, dtype, f, sh_degree, config, depth_range=(0.0, 0.0), tile_rows=None, projected=False,
-               capacity=0, depth16=False):
-  """(ms_frame_desc of a frame, the tile rows it renders)"""
+               capacity=0, depth16=False, active_degree=None):
+  """(ms_frame_desc of a frame, the tile rows it renders).  ``active_degree``: evaluate SH bands 0..active_degree of the
+  stored ``sh_degree`` only (``sh_active_bands``); None: all of them."""
   w, h, rows = RowWindow.of(image_size, config.tile_size, tile_rows)[:3]
   return _lib.FrameDescC(n=int(n), k_capacity=int(capacity), image_w=w, image_h=h, dtype=_lib.dtype_code(dtype), f=int(f),
                          sh_degree=int(sh_degree), depth16=int(depth16), tile_row_begin=rows[0], tile_row_end=rows[1],
-                         projected_input=int(projected), mapper=0, near_plane=float(depth_range[0]),
+                         projected_input=int(projected), mapper=0,
+                         sh_active_bands=0 if active_degree is None else int(active_degree) + 1,
+                         near_plane=float(depth_range[0]),
                          far_plane=float(depth_range[1]), blur_cov=float(config.blur_cov),
                          clamp_margin=float(config.clamp_margin), raster=_lib.raster_config_c(config)), rows
 
@@ -728,7 +732,7 @@ class _FrameFunction(torch.autograd.Function):
 
     key = _shape_key(device, n, (window.w, window.h), config, opts.tile_rows, opts.use_depth16)
     desc, _ = frame_desc(n, opts.image_size, dtype, f, degree, config, opts.depth_range, opts.tile_rows,
-                         depth16=opts.use_depth16)
+                         depth16=opts.use_depth16, active_degree=opts.sh_degree)
     image, alpha = window.alloc(dtype, device, f), window.alloc(dtype, device)
     visibility, heuristic = _point_outputs(n, config, dtype, device)
     state.window, state.placeholder = window, window.placeholder(dtype, device)
@@ -857,9 +861,11 @@ class _FrameFunction(torch.autograd.Function):
           total_c = grad_colours if (moments_path or g_colours is None) else grad_colours + g_colours
           g_cam = torch.zeros((3,), dtype=dtype, device=device)
           cam_pos = block_view(state.keep_n, state.layout.camera_position, dtype, (3,))
-          _lib.check(lib.ms_sh_bwd(feat.data_ptr(), pos.data_ptr(), identity_indexes(n, device).data_ptr(), cam_pos.data_ptr(),
-                                   n, f, ctx.degree, None, total_c.data_ptr(), None, None, g_cam.data_ptr(), 0,
-                                   _lib.dtype_code(dtype), stream), "render_gaussians backward (camera position)")
+          active = ctx.degree if opts.sh_degree is None else opts.sh_degree
+          _lib.check(lib.ms_sh_bwd_active(feat.data_ptr(), pos.data_ptr(), identity_indexes(n, device).data_ptr(),
+                                          cam_pos.data_ptr(), n, f, ctx.degree, active, None, total_c.data_ptr(), None, None,
+                                          g_cam.data_ptr(), 0, _lib.dtype_code(dtype), stream),
+                     "render_gaussians backward (camera position)")
           A = torch.inverse(Tcw)
           dA = torch.zeros((4, 4), dtype=dtype, device=device)
           dA[:3, 3] = g_cam
@@ -986,13 +992,14 @@ class LazyPoints:
 
 
 def render_frame(gaussians, camera_params, config: RasterConfig, use_sh: bool, use_depth16: bool = False,
-                 render_median_depth: bool = False, tile_rows=None, crop_to_rows: bool = False):
+                 render_median_depth: bool = False, tile_rows=None, crop_to_rows: bool = False,
+                 sh_degree: Optional[int] = None):
   """``render_gaussians`` on the frame executor.  Returns a ``Rendering`` whose ``points`` are built lazily."""
   from .rendering import Rendering
   opts = FrameOptions(image_size=tuple(int(x) for x in camera_params.image_size),
                       depth_range=tuple(float(x) for x in camera_params.depth_range), config=config,
                       use_sh=bool(use_sh), use_depth16=bool(use_depth16), tile_rows=tile_rows,
-                      crop_to_rows=bool(crop_to_rows), render_median_depth=bool(render_median_depth))
+                      crop_to_rows=bool(crop_to_rows), render_median_depth=bool(render_median_depth), sh_degree=sh_degree)
   state = FrameState()
   args = (*gaussians.shape_tensors(), gaussians.feature, camera_params.T_camera_world.reshape(4, 4),
           camera_params.projection.reshape(4))

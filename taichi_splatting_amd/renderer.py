@@ -16,7 +16,7 @@ from .perspective import CameraParams
 from .perspective.projection import project_to_image
 from .rasterizer.function import rasterize_with_tiles
 from .rendering import RenderedPoints, Rendering, ndc_depth
-from .spherical_harmonics import evaluate_sh_at
+from .spherical_harmonics import check_active_degree, check_sh_degree, evaluate_sh_at
 
 
 def render_gaussians(
@@ -28,6 +28,8 @@ def render_gaussians(
   use_depth16: bool = False,
   render_median_depth: bool = False,
   tile_rows: Optional[Tuple[int, int]] = None,
+  *,
+  sh_degree: Optional[int] = None,
 ) -> Rendering:
   """A complete renderer for 3D gaussians.
 
@@ -40,12 +42,19 @@ def render_gaussians(
     use_depth16: 16 bit depth sort keys (otherwise 32 bit)
     render_median_depth: extra quantile pass producing ``median_depth_image``
     tile_rows: optional (begin, end) tile-row strip to render (multi-GPU sharding)
+    sh_degree: active SH degree, 0..D for features stored at degree D (needs ``use_sh``): bands above it are neither
+      evaluated nor trained — colours of ``feature[:, :, :(sh_degree + 1)**2]``, zero gradient for the rest.  ``None``:
+      every stored band.  Out of range raises ``ValueError``; nothing is clamped.
   """
   from . import frame
+  if sh_degree is not None:
+    if not use_sh:
+      raise ValueError("render_gaussians: sh_degree needs use_sh=True (the features are plain colours otherwise)")
+    sh_degree = check_active_degree(sh_degree, check_sh_degree(gaussians.feature), "render_gaussians: sh_degree")
   if frame.USE_FRAME and frame.frame_supported(gaussians.feature, config, use_sh):
     # one autograd node on a fixed launch sequence, no host round trip for the visible / overlap counts (frame.py)
     return frame.render_frame(gaussians, camera_params, config, use_sh, use_depth16=use_depth16,
-                              render_median_depth=render_median_depth, tile_rows=tile_rows)
+                              render_median_depth=render_median_depth, tile_rows=tile_rows, sh_degree=sh_degree)
 
   # modular composition (wide feature vectors, MS_FRAME=legacy): launched before the projection's host
   # synchronisation (visible count) so that the first kernel queued after it is the long SH pass
@@ -54,7 +63,7 @@ def render_gaussians(
 
   if use_sh:
     features = evaluate_sh_at(gaussians.feature, gaussians.position.detach(), indexes,
-                              camera_position, unique_indexes=True)
+                              camera_position, unique_indexes=True, active_degree=sh_degree)
   else:
     features = gaussians.feature[indexes]
     assert len(features.shape) == 2, f"Features must be (N, C) if use_sh=False, got {features.shape}"

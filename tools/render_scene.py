@@ -9,7 +9,9 @@ read (file -> pinned staging buffer, host seconds) and upload / unpack (device e
 gaussians and tile overlaps; ms per frame is the median over the views after one warm-up pass over all of them.  With
 --out the images are written as view_000.npy ... (H, W, 3) float32.
 
-    python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR]
+    python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d]
+
+--sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 """
 import argparse
 import json
@@ -61,6 +63,8 @@ def main():
   p.add_argument('--size', type=int, nargs=2, default=(1024, 768), metavar=('W', 'H'))
   p.add_argument('--views', type=int, default=8)
   p.add_argument('--out', default='')
+  p.add_argument('--sh-degree', type=int, default=None, metavar='d',
+                 help="active SH degree: render bands 0..d of the file's degree only (default: all of them)")
   args = p.parse_args()
   if not torch.cuda.is_available():
     sys.exit("render_scene: no GPU visible (the renderer has no CPU fallback)")
@@ -78,20 +82,22 @@ def main():
   if n == 0:
     sys.exit(f"render_scene: {args.scene} holds no gaussians")
   degree = math.isqrt(gaussians.feature.shape[2]) - 1
+  if args.sh_degree is not None and not 0 <= args.sh_degree <= degree:
+    sys.exit(f"render_scene: --sh-degree {args.sh_degree} is outside 0..{degree}, the degree of {args.scene}")
   cameras, radius = orbit_cameras(gaussians.position, args.views, tuple(args.size), device)
   config = RasterConfig()
 
   visible, overlaps, frame_ms, images = [], [], [], []
   with torch.no_grad():
     for camera in cameras:                          # warm-up: every view once (capacities, mapper choice, allocator)
-      rendering = render_gaussians(gaussians, camera, config, use_sh=True)
+      rendering = render_gaussians(gaussians, camera, config, use_sh=True, sh_degree=args.sh_degree)
       visible.append(int(rendering.points.idx.shape[0]))
       overlaps.append(int(frame.frame_status(rendering)['overlaps']) if hasattr(rendering, 'frame') else None)
     torch.cuda.synchronize()
     for camera in cameras:
       begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
       begin.record()
-      rendering = render_gaussians(gaussians, camera, config, use_sh=True)
+      rendering = render_gaussians(gaussians, camera, config, use_sh=True, sh_degree=args.sh_degree)
       end.record()
       end.synchronize()
       frame_ms.append(begin.elapsed_time(end))
@@ -102,7 +108,7 @@ def main():
     for v, image in enumerate(images):
       np.save(out / f'view_{v:03d}.npy', image.cpu().numpy())
   print(json.dumps(dict(
-    scene=str(args.scene), n=n, sh_degree=degree, image_size=list(args.size), views=args.views, orbit_radius=round(radius, 6),
+    scene=str(args.scene), n=n, sh_degree=degree, sh_active_degree=args.sh_degree, image_size=list(args.size), views=args.views, orbit_radius=round(radius, 6),
     load_s=round(load_s, 4), read_s=round(timings['read_s'], 4), upload_ms=round(timings['upload_ms'], 3),
     unpack_ms=round(timings['unpack_ms'], 3), visible=visible, overlaps=overlaps,
     frame_ms=round(statistics.median(frame_ms), 4), frame_ms_per_view=[round(ms, 4) for ms in frame_ms],
