@@ -748,6 +748,42 @@ int ms_photometric_bwd(const void* image, const void* target, const void* map_a,
                        const void* grad_out, int H, int W, int C, int dtype, int padding, double lambda,
                        void* grad_image, void* stream);
 
+/* ---- Scene transform: a similarity m = [[s R, t], [0, 1]] on a whole 3-D scene in one launch (csrc/scene_transform.hip) --
+ * An addition: the reference's transform_rigid (data_types.py:91-102) moves position and rotation and leaves the SH
+ * coefficients alone, so the view-dependent colour of a rotated scene points the old way.
+ *   position'    = s R p + t
+ *   log_scaling' = log_scaling + ln s
+ *   rotation'    = q_R (x) q   (Hamilton product, xyzw; the row is NOT normalised — the kernels normalise on read — and a
+ *                               zero row stays zero)
+ *   feature'     : (n, f, (sh_degree + 1)^2); in the real basis of ms_sh_fwd, band l (coefficients l^2 .. (l + 1)^2 - 1)
+ *                  of every (gaussian, channel) is replaced by M_l(R) c_l, where Y_l(R d) = M_l(R) Y_l(d) for every unit
+ *                  d: the moved scene shows from the moved camera what the old one showed from the old.  Band 0 is
+ *                  invariant.  alpha_logit and (n, C) colours do not change and are not arguments.
+ * Each field is an (in, out) pair of (n, 3 | 3 | 4 | f K) arrays of `dtype`; a pair of NULLs skips the field, out == in
+ * works in place, any other overlap is the caller's error.  sh_degree must be 1..3 and f >= 1 when a feature is given
+ * (a degree-0 feature has nothing to rotate: pass NULLs).  Pointers need only the alignment of their element type: a
+ * feature whose two bases are 16-byte aligned moves in 16-byte pieces, any other in 4-byte pieces.
+ * transform_host: MS_SCENE_XFORM_VALUES doubles in HOST memory, read during the call and passed on as kernel arguments
+ * (no device buffer, no host read of device memory, no allocation, no synchronisation: the call can be captured into a
+ * graph): [s R | t] row-major 3x4, ln s, q_R (xyzw), then M_1 (3x3), M_2 (5x5), M_3 (7x7) row-major (the matrices
+ * above sh_degree are not read).  The geometry is evaluated in double and rounded once; the matrices are rounded to
+ * `dtype` and applied with FMAs.  A workgroup takes MS_SCENE_XFORM_ROWS consecutive rows.
+ * n == 0: returns 0 without a launch.  MS_ERR_BAD_ARG: n < 0 or >= 2^31, sh_degree outside 1..3 or f < 1 with a feature,
+ * one pointer of a pair NULL and the other not, unknown dtype, NULL transform_host, a misaligned pointer. */
+#define MS_SCENE_XFORM_ROWS 256
+enum {
+  MS_SCENE_XFORM_SRT = 0,      /* 12 values */
+  MS_SCENE_XFORM_LN_S = 12,
+  MS_SCENE_XFORM_QUAT = 13,    /* 4 values */
+  MS_SCENE_XFORM_M1 = 17,      /* 9 values */
+  MS_SCENE_XFORM_M2 = 26,      /* 25 values */
+  MS_SCENE_XFORM_M3 = 51,      /* 49 values */
+  MS_SCENE_XFORM_VALUES = 100
+};
+int ms_scene_transform(const void* position, void* out_position, const void* log_scaling, void* out_log_scaling,
+                       const void* rotation, void* out_rotation, const void* feature, void* out_feature,
+                       int64_t n, int f, int sh_degree, int dtype, const double* transform_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

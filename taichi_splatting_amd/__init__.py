@@ -10,7 +10,7 @@ from .rendering import Rendering, RenderedPoints
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
 from .rasterizer import rasterize, rasterize_with_tiles, RasterOut
-from .spherical_harmonics import evaluate_sh_at
+from .spherical_harmonics import evaluate_sh_at, sh_rotation_matrices, rotate_sh
 from . import perspective
 from . import cuda_lib
 from . import cuda_lib as hip_lib
@@ -26,7 +26,7 @@ __all__ = [
   'render_gaussians', 'Rendering',
   'map_to_tiles', 'pad_to_tile',
   'Gaussians2D', 'Gaussians3D',
-  'RasterConfig', 'evaluate_sh_at',
+  'RasterConfig', 'evaluate_sh_at', 'sh_rotation_matrices', 'rotate_sh',
   'rasterize', 'rasterize_with_tiles',
   'perspective', 'TaichiQueue',
   'l1_ssim_loss', 'ssim',

@@ -28,6 +28,8 @@ PAD_SAME, PAD_VALID = 0, 1                         # MS_PAD_SAME / MS_PAD_VALID 
 MOMENT_ROW = 16   # MS_MOMENT_ROW of include/mi355_splat.h
 SPLAT_ROW = 16    # MS_SPLAT_ROW
 KNN_BLOCK = 256   # MS_KNN_BLOCK: sorted points per block of ms_knn_points
+SCENE_XFORM_ROWS = 256     # MS_SCENE_XFORM_ROWS: rows per workgroup of ms_scene_transform
+SCENE_XFORM_VALUES = 100   # MS_SCENE_XFORM_VALUES: doubles of its host transform array
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -191,6 +193,7 @@ SIGNATURES = {
   'ms_densify_split3d': (c_int, [c_void_p] * 3 + [c_int64, c_int64, c_int] + [c_void_p] * 3),
   'ms_photometric_fwd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p, c_void_p]),
   'ms_photometric_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
+  'ms_scene_transform': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, POINTER(c_double), c_void_p]),
 }
 
 

@@ -129,13 +129,62 @@ class Gaussians3D(TensorClass):
     return torch.sigmoid(self.alpha_logit)
 
   def transform_rigid(self, m: torch.Tensor) -> 'Gaussians3D':
-    """Transform the gaussians by a rigid 4x4 matrix (reference ``data_types.py:91-102``)."""
+    """Transform the gaussians by a rigid 4x4 matrix (reference ``data_types.py:91-102``).
+    Like the reference it leaves SH coefficients alone; ``transformed`` rotates them too."""
     assert m.shape == (4, 4), f"Expected shape (4, 4), got {m.shape}"
     r, t = m[:3, :3], m[:3, 3]
     position = self.position @ r.T + t
     q = self.rotation / torch.norm(self.rotation, dim=-1, keepdim=True)
     rotation = _mat_to_quat(r.unsqueeze(0) @ _quat_to_mat(q))
     return self.replace(position=position, rotation=rotation)
+
+  def transformed(self, m: torch.Tensor, *, rotate_sh: bool = True, inplace: bool = False) -> 'Gaussians3D':
+    """The scene in another world frame: ``m = [[s R, t], [0, 1]]`` with ``R`` a proper rotation and ``s > 0``, applied
+    by one kernel launch (``ms_scene_transform``, csrc/scene_transform.hip; no reference counterpart).
+
+    ``position' = s R p + t``, ``log_scaling' = log_scaling + ln s``, ``rotation' = q_R (x) q`` (xyzw; the row is not
+    normalised, the kernels normalise on read), ``alpha_logit`` unchanged.  SH features (N, F, (D+1)^2) are rotated band
+    by band, ``c'_l = M_l(R) c_l`` (``spherical_harmonics.sh_rotation_matrices``), so that the moved scene shows from
+    the moved camera ``diag(s, s, s, 1) T_camera_world m^-1`` (near and far times ``s``) what the old one showed from
+    the old; ``rotate_sh=False`` leaves them alone, which is what ``transform_rigid`` does.  (N, C) colours and degree-0
+    features do not change and are shared with ``self``.
+
+    ``inplace=True`` writes into the scene's own tensors (no N x 48 temporary) and returns ``self``; tensors that
+    require grad are refused outside ``torch.no_grad()``.  The tensors must be on the GPU, float32 or float64.
+    ``m`` is validated on the host in float64: a reflection, shear or non-uniform scale raises ``ValueError``.
+
+    Out of scope: gradients with respect to ``m`` (the result is detached from ``self``), optimiser moments (the second
+    moment does not transform linearly: reset the optimiser state of a transformed scene) and reflections."""
+    from . import _lib
+    from .spherical_harmonics import pack_scene_transform, scene_transform, check_sh_degree
+    s, r, t = similarity_from_matrix(m)
+    geometry = (self.position, self.log_scaling, self.rotation)
+    _lib.require_gpu(*geometry, self.feature)
+    for x in (*geometry, self.feature):
+      _lib.dtype_code(x.dtype)
+    degree = check_sh_degree(self.feature) if self.feature.ndim == 3 else 0
+    if not 0 <= degree <= 3:
+      raise ValueError(f"SH degree must be between 0 and 3, got {degree}")
+    with_feature = bool(rotate_sh) and degree >= 1
+    fields = geometry + ((self.feature,) if with_feature else ())
+    if not all(x.dtype == self.position.dtype and x.is_contiguous() for x in fields):
+      raise ValueError("transformed: contiguous tensors of one dtype expected")
+    if inplace:
+      if torch.is_grad_enabled() and any(x.requires_grad for x in fields):
+        raise RuntimeError("transformed(inplace=True) would overwrite tensors that require grad: "
+                           "call it under torch.no_grad()")
+      outs = [x.detach() for x in fields]
+    else:
+      outs = [torch.empty_like(x, requires_grad=False) for x in fields]
+    packed = pack_scene_transform(s, r, t, max(degree, 1))
+    ins = [x.detach() for x in fields]
+    scene_transform(packed, position=ins[0], log_scaling=ins[1], rotation=ins[2], feature=ins[3] if with_feature else None,
+                    out_position=outs[0], out_log_scaling=outs[1], out_rotation=outs[2],
+                    out_feature=outs[3] if with_feature else None)
+    if inplace:
+      return self
+    return self.replace(position=outs[0], log_scaling=outs[1], rotation=outs[2],
+                        feature=outs[3] if with_feature else self.feature)
 
   @staticmethod
   def concat_batch(gaussians: List['Gaussians3D']) -> 'Gaussians3D':
@@ -197,6 +246,29 @@ class Gaussians3D(TensorClass):
     """Write the scene as a binary 3DGS PLY file (``scene_io.save_ply``)."""
     from .scene_io import save_ply
     save_ply(self, path, chunk_rows=chunk_rows)
+
+
+def similarity_from_matrix(m) -> Tuple[float, torch.Tensor, torch.Tensor]:
+  """``(s, R, t)`` of ``m = [[s R, t], [0, 1]]``, float64 on the CPU, or ``ValueError``: ``m`` must be (4, 4) with last
+  row (0, 0, 0, 1), ``s = det(m[:3, :3])^(1/3) > 0`` and ``m[:3, :3] / s`` a proper rotation."""
+  from .spherical_harmonics import check_rotation
+  if not isinstance(m, torch.Tensor) or m.shape != (4, 4):
+    raise ValueError(f"m must be a (4, 4) tensor, got {tuple(getattr(m, 'shape', ()))}")
+  m = m.detach().to(device='cpu', dtype=torch.float64)
+  if not bool(torch.isfinite(m).all()):
+    raise ValueError("m has non-finite entries")
+  if m[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
+    raise ValueError(f"the last row of m must be (0, 0, 0, 1), got {tuple(m[3].tolist())}")
+  why = "a quaternion and an isotropic log_scaling offset cannot represent it"
+  det = float(torch.linalg.det(m[:3, :3]))
+  if not det > 0:
+    raise ValueError(f"m[:3, :3] has determinant {det:.3g}: a reflection or a singular matrix; {why}")
+  s = det ** (1.0 / 3.0)
+  try:
+    r = check_rotation(m[:3, :3] / s, "m[:3, :3] / s")
+  except ValueError as e:
+    raise ValueError(f"m is not a similarity transform ({e}); {why}") from None
+  return s, r, m[:3, 3].clone()
 
 
 def inverse_sigmoid(x: torch.Tensor):

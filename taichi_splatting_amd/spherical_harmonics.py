@@ -2,9 +2,14 @@
 
 Same interface as reference ``indexed_spherical_harmonics.py:166-177`` (``evaluate_sh_at``);
 forward/backward kernels in csrc/sh.hip (hand-derived backward instead of Taichi autodiff).
+
+``sh_rotation_matrices`` / ``rotate_sh`` (no reference counterpart) rotate the bands of stored coefficients, the SH half
+of ``Gaussians3D.transformed`` (csrc/scene_transform.hip).
 """
 from __future__ import annotations
 
+import ctypes
+import functools
 import math
 from typing import Optional
 
@@ -92,3 +97,174 @@ def evaluate_sh_at(sh_params: torch.Tensor,   # M, K, (degree + 1)^2  (usually K
   assert 0 <= degree <= 3, f"SH degree must be between 0 and 3, got {degree}"
   active = check_active_degree(active_degree, degree)
   return _SHFunction.apply(sh_params, positions, indexes, camera_pos, degree, unique_indexes, active)
+
+
+# ---- rotating the bands: Gaussians3D.transformed / ms_scene_transform (csrc/scene_transform.hip) ------------------------
+
+def _rsh_cart_f64(xyz: torch.Tensor, degree: int) -> torch.Tensor:
+  """The real basis of csrc/splat_math.h (``sh_basis``) at unit directions (M, 3), float64 on the host: (M, (degree+1)^2)."""
+  x, y, z = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+  out = [torch.full_like(x, 0.282094791773878)]
+  if degree >= 1:
+    out += [-0.48860251190292 * y, 0.48860251190292 * z, -0.48860251190292 * x]
+  if degree >= 2:
+    x2, y2, z2 = x * x, y * y, z * z
+    out += [1.09254843059208 * (x * y), -1.09254843059208 * (y * z), 0.94617469575756 * z2 - 0.31539156525252,
+            -1.09254843059208 * (x * z), 0.54627421529604 * x2 - 0.54627421529604 * y2]
+  if degree >= 3:
+    out += [-0.590043589926644 * y * (3.0 * x2 - y2), 2.89061144264055 * (x * y) * z,
+            0.304697199642977 * y * (1.5 - 7.5 * z2), 1.24392110863372 * z * (1.5 * z2 - 0.5) - 0.497568443453487 * z,
+            0.304697199642977 * x * (1.5 - 7.5 * z2), 1.44530572132028 * z * (x2 - y2),
+            -0.590043589926644 * x * (x2 - 3.0 * y2)]
+  return torch.stack(out, dim=-1)
+
+
+@functools.lru_cache(maxsize=None)
+def _solve_directions():
+  """(D, pinv(Y_1(D)), pinv(Y_2(D)), pinv(Y_3(D))) for 48 fixed unit directions D (a Fibonacci spiral): the band blocks
+  of the basis sampled there have condition numbers below 1.05, so the least-squares solve of
+  ``sh_rotation_matrices`` loses no digits.  Computed once per process."""
+  k = torch.arange(48, dtype=torch.float64) + 0.5
+  z = 1.0 - 2.0 * k / 48.0
+  phi = k * (math.pi * (3.0 - math.sqrt(5.0)))
+  r = torch.sqrt(1.0 - z * z)
+  dirs = torch.stack([r * torch.cos(phi), r * torch.sin(phi), z], dim=-1)
+  y = _rsh_cart_f64(dirs, 3)
+  return (dirs,) + tuple(torch.linalg.pinv(y[:, l * l:(l + 1) * (l + 1)]) for l in (1, 2, 3))
+
+
+def _mul_sum(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+  """a (I, K) times b (K, J) as products summed in index order: the same bits on every call, which a threaded BLAS or
+  LAPACK does not promise (the in-place and out-of-place forms of a transform must agree bit for bit)."""
+  out = torch.zeros((a.shape[0], b.shape[1]), dtype=torch.float64)
+  for k in range(a.shape[1]):
+    out += a[:, k:k + 1] * b[k:k + 1, :]
+  return out
+
+
+def check_rotation(R, what: str = "R") -> torch.Tensor:
+  """``R`` as a float64 CPU (3, 3) proper rotation, or ``ValueError``: ``|R^T R - I|_inf <= 1e-5`` and ``det > 0``."""
+  if not isinstance(R, torch.Tensor) or R.shape != (3, 3):
+    raise ValueError(f"{what} must be a (3, 3) tensor, got {tuple(getattr(R, 'shape', ()))}")
+  R = R.detach().to(device='cpu', dtype=torch.float64)
+  if not bool(torch.isfinite(R).all()):
+    raise ValueError(f"{what} has non-finite entries")
+  off = float((R.T @ R - torch.eye(3, dtype=torch.float64)).abs().max())
+  if off > 1e-5:
+    raise ValueError(f"{what} is not a rotation: |R^T R - I| = {off:.3g} > 1e-5 (shear or non-uniform scale)")
+  if not float(torch.linalg.det(R)) > 0:
+    raise ValueError(f"{what} is a reflection (det < 0), not a rotation")
+  return R
+
+
+def sh_rotation_matrices(R: torch.Tensor, degree: int) -> list:
+  """``[M_0 .. M_degree]``, float64 on the CPU, ``M_l`` of shape (2l+1, 2l+1) with ``Y_l(R d) = M_l Y_l(d)`` for every
+  unit ``d`` in the basis of ``evaluate_sh_at`` (band l = coefficients l^2 .. (l+1)^2 - 1).  A scene rotated by ``R``
+  keeps its colours when every band of coefficients is replaced by ``M_l c_l``.  ``M_1 = P R P^T`` with
+  ``P = [[0,-1,0],[0,0,1],[-1,0,0]]`` (band 1 is k (-y, z, -x)).
+
+  Solved exactly from the basis at a fixed, well-conditioned set of directions: ``M_l = Y_l(R D) pinv(Y_l(D))``."""
+  if not isinstance(degree, int) or isinstance(degree, bool) or not 0 <= degree <= 3:
+    raise ValueError(f"degree must be an integer in 0..3, got {degree!r}")
+  R = check_rotation(R)
+  dirs, *pinv = _solve_directions()
+  y1 = _rsh_cart_f64(_mul_sum(dirs, R.T), degree)
+  out = [torch.ones((1, 1), dtype=torch.float64)]
+  for l in range(1, degree + 1):
+    # rows are directions: Y_l(R D) = Y_l(D) M^T  =>  M^T = pinv(Y_l(D)) Y_l(R D)
+    out.append(_mul_sum(pinv[l - 1], y1[:, l * l:(l + 1) * (l + 1)]).T.contiguous())
+  return out
+
+
+def rotation_to_quat(R: torch.Tensor) -> torch.Tensor:
+  """The unit xyzw quaternion of a rotation matrix, float64 on the CPU, with w >= 0: the largest component from the
+  diagonal, the other three from the off-diagonal sums and differences divided by it, so that every component is good
+  to a few 1e-16 (``data_types._mat_to_quat`` takes four square roots and loses half the digits of a small component)."""
+  m = check_rotation(R).tolist()
+  four_sq = (1.0 + m[0][0] - m[1][1] - m[2][2], 1.0 - m[0][0] + m[1][1] - m[2][2], 1.0 - m[0][0] - m[1][1] + m[2][2],
+             1.0 + m[0][0] + m[1][1] + m[2][2])                                      # 4 x^2, 4 y^2, 4 z^2, 4 w^2
+  k = max(range(4), key=lambda i: four_sq[i])
+  big = 0.5 * math.sqrt(four_sq[k])
+  d = 4.0 * big
+  if k == 3:
+    q = [(m[2][1] - m[1][2]) / d, (m[0][2] - m[2][0]) / d, (m[1][0] - m[0][1]) / d, big]
+  elif k == 0:
+    q = [big, (m[0][1] + m[1][0]) / d, (m[0][2] + m[2][0]) / d, (m[2][1] - m[1][2]) / d]
+  elif k == 1:
+    q = [(m[0][1] + m[1][0]) / d, big, (m[1][2] + m[2][1]) / d, (m[0][2] - m[2][0]) / d]
+  else:
+    q = [(m[0][2] + m[2][0]) / d, (m[1][2] + m[2][1]) / d, big, (m[1][0] - m[0][1]) / d]
+  norm = math.sqrt(sum(c * c for c in q))
+  sign = -1.0 if q[3] < 0 else 1.0
+  return torch.tensor([sign * c / norm for c in q], dtype=torch.float64)
+
+
+def pack_scene_transform(s: float, R: torch.Tensor, t: torch.Tensor, degree: int = 3):
+  """The host array of ``ms_scene_transform`` (MS_SCENE_XFORM_* of include/mi355_splat.h): ``[s R | t]``, ``ln s``,
+  ``q_R`` (xyzw), ``M_1 .. M_degree`` (the matrices above ``degree`` stay zero: the kernel does not read them)."""
+  R = check_rotation(R)
+  if not (s > 0 and math.isfinite(s)):
+    raise ValueError(f"scale must be positive and finite, got {s}")
+  t = t.detach().to(device='cpu', dtype=torch.float64).reshape(3)
+  values = torch.zeros(_lib.SCENE_XFORM_VALUES, dtype=torch.float64)
+  values[:12] = torch.cat([s * R, t.view(3, 1)], dim=1).reshape(12)
+  values[12] = math.log(s)
+  values[13:17] = rotation_to_quat(R)
+  at = 17
+  for m in sh_rotation_matrices(R, degree)[1:]:
+    values[at:at + m.numel()] = m.reshape(-1)
+    at += m.numel()
+  return (ctypes.c_double * _lib.SCENE_XFORM_VALUES)(*values.tolist())
+
+
+def scene_transform(packed, *, position=None, log_scaling=None, rotation=None, feature=None, out_position=None,
+                    out_log_scaling=None, out_rotation=None, out_feature=None) -> None:
+  """One ``ms_scene_transform`` launch on the current stream: each given field from its tensor into its ``out_`` tensor
+  (the same tensor: in place).  ``feature`` is (N, F, (D+1)^2) with D in 1..3.  No host read, no allocation."""
+  pairs = ((position, out_position, 3), (log_scaling, out_log_scaling, 3), (rotation, out_rotation, 4), (feature, out_feature, None))
+  given = [p for p in pairs if p[0] is not None]
+  assert given, "scene_transform: no field given"
+  _lib.require_gpu(*[x for p in given for x in p[:2]])
+  first = given[0][0]
+  n, f, degree = first.shape[0], 1, 0
+  for src, dst, width in given:
+    assert dst is not None and dst.shape == src.shape and dst.dtype == first.dtype and src.dtype == first.dtype \
+      and dst.device == first.device and src.device == first.device, "scene_transform: out tensors must match their inputs"
+    assert src.is_contiguous() and dst.is_contiguous(), "scene_transform: contiguous tensors expected"
+    assert src.shape[0] == n and (width is None or src.shape[1:] == (width,)), f"scene_transform: unexpected shape {tuple(src.shape)}"
+  if feature is not None:
+    degree = check_sh_degree(feature)
+    f = feature.shape[1]
+  p = lambda x: None if x is None else x.data_ptr()
+  _lib.check(_lib.load().ms_scene_transform(p(position), p(out_position), p(log_scaling), p(out_log_scaling), p(rotation),
+                                            p(out_rotation), p(feature), p(out_feature), n, f, degree,
+                                            _lib.dtype_code(first.dtype), packed, _lib.current_stream(first.device)),
+             "scene_transform")
+
+
+def rotate_sh(feature: torch.Tensor, R: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """The SH coefficients (N, F, (D+1)^2) of a scene rotated by ``R``: every band replaced by ``M_l(R) c_l``
+  (``sh_rotation_matrices``), one launch on the GPU.  ``out=feature`` works in place.  A degree-0 feature has nothing
+  to rotate: it is returned as it is (``out=None``) or copied into ``out``.  No gradient flows through this call."""
+  degree = check_sh_degree(feature)
+  assert 0 <= degree <= 3, f"SH degree must be between 0 and 3, got {degree}"
+  R = check_rotation(R)
+  _lib.require_gpu(feature, out)
+  _lib.dtype_code(feature.dtype)
+  if out is not None and (out.shape != feature.shape or out.dtype != feature.dtype or out.device != feature.device):
+    raise ValueError(f"out must match feature: {tuple(feature.shape)} {feature.dtype} on {feature.device}")
+  if degree == 0:
+    if out is None:
+      return feature
+    if out is not feature:
+      out.copy_(feature)
+    return out
+  src = feature.detach()
+  src = src if src.is_contiguous() else src.contiguous()
+  if out is None:
+    out = torch.empty_like(src)
+  if not out.is_contiguous():
+    raise ValueError("out must be contiguous")
+  packed = pack_scene_transform(1.0, R, torch.zeros(3), degree)
+  scene_transform(packed, feature=src, out_feature=out.detach())
+  return out

@@ -9,9 +9,12 @@ read (file -> pinned staging buffer, host seconds) and upload / unpack (device e
 gaussians and tile overlaps; ms per frame is the median over the views after one warm-up pass over all of them.  With
 --out the images are written as view_000.npy ... (H, W, 3) float32.
 
-    python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d]
+    python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d] [--transform "x 90 0.5"]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
+--transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
+similarity matrix) moves the scene after loading, SH bands included (Gaussians3D.transformed, in place); the cameras
+orbit the moved scene.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from taichi_splatting_amd import CameraParams, RasterConfig, frame, render_gaussians, scene_io     # noqa: E402
+from taichi_splatting_amd.data_types import similarity_from_matrix                                 # noqa: E402
 
 
 def orbit_cameras(position, views, size, device):
@@ -57,6 +61,22 @@ def orbit_cameras(position, views, size, device):
   return cameras, radius
 
 
+def parse_transform(text):
+  """'AXIS DEG [SCALE]' or 16 numbers -> (4, 4) float64; what the matrix may be is Gaussians3D.transformed's to check"""
+  tokens = text.replace(',', ' ').split()
+  if len(tokens) == 16:
+    return torch.tensor([float(x) for x in tokens], dtype=torch.float64).reshape(4, 4)
+  if len(tokens) not in (2, 3) or tokens[0].lower() not in ('x', 'y', 'z'):
+    raise ValueError(f'--transform expects "AXIS DEG [SCALE]" with AXIS one of x, y, z, or 16 numbers; got {text!r}')
+  axis, angle = 'xyz'.index(tokens[0].lower()), math.radians(float(tokens[1]))
+  scale = float(tokens[2]) if len(tokens) == 3 else 1.0
+  i, j = (axis + 1) % 3, (axis + 2) % 3
+  m = torch.eye(4, dtype=torch.float64)
+  m[i, i], m[i, j], m[j, i], m[j, j] = math.cos(angle), -math.sin(angle), math.sin(angle), math.cos(angle)
+  m[:3, :3] *= scale
+  return m
+
+
 def main():
   p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
   p.add_argument('scene')
@@ -65,7 +85,16 @@ def main():
   p.add_argument('--out', default='')
   p.add_argument('--sh-degree', type=int, default=None, metavar='d',
                  help="active SH degree: render bands 0..d of the file's degree only (default: all of them)")
+  p.add_argument('--transform', default=None, metavar='"AXIS DEG [SCALE]"',
+                 help="move the loaded scene: a rotation about x, y or z in degrees and a uniform scale, or 16 numbers "
+                      "(row-major 4x4 similarity matrix); SH bands are rotated with it")
   args = p.parse_args()
+  try:
+    transform = parse_transform(args.transform) if args.transform is not None else None
+    if transform is not None:
+      similarity_from_matrix(transform)             # (refused before the file is read)
+  except ValueError as e:
+    sys.exit(f"render_scene: --transform: {e}")
   if not torch.cuda.is_available():
     sys.exit("render_scene: no GPU visible (the renderer has no CPU fallback)")
   if args.views < 1:
@@ -84,6 +113,9 @@ def main():
   degree = math.isqrt(gaussians.feature.shape[2]) - 1
   if args.sh_degree is not None and not 0 <= args.sh_degree <= degree:
     sys.exit(f"render_scene: --sh-degree {args.sh_degree} is outside 0..{degree}, the degree of {args.scene}")
+  if transform is not None:
+    with torch.no_grad():
+      gaussians.transformed(transform, inplace=True)
   cameras, radius = orbit_cameras(gaussians.position, args.views, tuple(args.size), device)
   config = RasterConfig()
 
@@ -108,7 +140,7 @@ def main():
     for v, image in enumerate(images):
       np.save(out / f'view_{v:03d}.npy', image.cpu().numpy())
   print(json.dumps(dict(
-    scene=str(args.scene), n=n, sh_degree=degree, sh_active_degree=args.sh_degree, image_size=list(args.size), views=args.views, orbit_radius=round(radius, 6),
+    scene=str(args.scene), n=n, sh_degree=degree, sh_active_degree=args.sh_degree, transform=args.transform, image_size=list(args.size), views=args.views, orbit_radius=round(radius, 6),
     load_s=round(load_s, 4), read_s=round(timings['read_s'], 4), upload_ms=round(timings['upload_ms'], 3),
     unpack_ms=round(timings['unpack_ms'], 3), visible=visible, overlaps=overlaps,
     frame_ms=round(statistics.median(frame_ms), 4), frame_ms_per_view=[round(ms, 4) for ms in frame_ms],
