@@ -784,6 +784,37 @@ int ms_scene_transform(const void* position, void* out_position, const void* log
                        const void* rotation, void* out_rotation, const void* feature, void* out_feature,
                        int64_t n, int f, int sh_degree, int dtype, const double* transform_host, void* stream);
 
+/* ---- Camera-set coverage: which cameras see each gaussian, in one launch (csrc/camera_coverage.hip) -------------------
+ * An addition: neither the reference nor ms_project_fwd looks at a scene through more than one camera at a time, so
+ * "which gaussians does no training view render", "by how many views is each seen" and "at what sampling rate" cost a
+ * loop of projections, one host read of the visible count and one index tensor per camera.
+ * One lane per gaussian loops over all cameras.  "In view" is bit for bit the decision ms_project_fwd takes for that
+ * camera with its own image size and clip planes and this call's blur_cov, clamp_margin and alpha_threshold — the
+ * alpha-below-threshold NaN path and a zero or non-finite quaternion included, both culled.
+ *   out_count     (n) int32: number of cameras that have gaussian i in view
+ *   out_max_rate  (n) `dtype`: max over those cameras of max(fx, fy) / z, one division in `dtype`, z the camera-space
+ *                 depth ms_project_fwd writes; 0 where out_count is 0.  The sampling rate Mip-Splatting's 3-D filter
+ *                 is built from.
+ *   out_min_depth (n) `dtype`: min over those cameras of z; +inf where out_count is 0
+ *   out_mask      NULL, or (ceil(num_cameras / 32), n) uint32, WORD-major: bit c % 32 of out_mask[(c / 32) * n + i] is
+ *                 set exactly when camera c has gaussian i in view; unused high bits of the last word are zero.
+ * cameras: a DEVICE array (num_cameras, MS_COVERAGE_CAMERA_VALUES) of `dtype`, per camera: rows 0..2 of T_camera_world
+ * row-major (12 values), fx, fy, cx, cy, near, far, width, height.  Every lane reads it wave-uniformly (scalar loads).
+ * position (n, 3), log_scaling (n, 3), rotation (n, 4), alpha_logit (n) as for ms_project_fwd; dtype MS_F32 or MS_F64.
+ * No atomics: the outputs are bitwise reproducible.  No allocation, no synchronisation, no host read of device memory:
+ * the call can be captured into a graph.  n == 0: returns 0 without a launch.  Every argument is checked before the
+ * launch; MS_ERR_BAD_ARG: n < 0 or >= 2^31, num_cameras outside 1..MS_COVERAGE_MAX_CAMERAS, unknown dtype, a pointer not
+ * aligned to its element type, a NULL pointer other than out_mask with n > 0.
+ * Measured on an MI355X, 6 M random gaussians, float32, masks included: 16 / 64 / 256 cameras in 0.80 / 2.99 / 11.8 ms
+ * (130 G pairs per second, the same without masks), against 5.0 / 19.7 / 78.8 ms for the loop of ms_project_fwd, scan, host
+ * read, gather and torch scatters it replaces: 6.2 - 6.7 x (profiles/camera_coverage.txt). */
+#define MS_COVERAGE_CAMERA_VALUES 20
+#define MS_COVERAGE_MAX_CAMERAS 65535
+int ms_camera_coverage(const void* position, const void* log_scaling, const void* rotation, const void* alpha_logit,
+                       const void* cameras, int num_cameras, double blur_cov, double clamp_margin,
+                       double alpha_threshold, int64_t n, int32_t* out_count, void* out_max_rate, void* out_min_depth,
+                       uint32_t* out_mask /* may be NULL */, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

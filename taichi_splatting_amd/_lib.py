@@ -30,6 +30,8 @@ SPLAT_ROW = 16    # MS_SPLAT_ROW
 KNN_BLOCK = 256   # MS_KNN_BLOCK: sorted points per block of ms_knn_points
 SCENE_XFORM_ROWS = 256     # MS_SCENE_XFORM_ROWS: rows per workgroup of ms_scene_transform
 SCENE_XFORM_VALUES = 100   # MS_SCENE_XFORM_VALUES: doubles of its host transform array
+COVERAGE_CAMERA_VALUES = 20     # MS_COVERAGE_CAMERA_VALUES: values per camera row of ms_camera_coverage
+COVERAGE_MAX_CAMERAS = 65535    # MS_COVERAGE_MAX_CAMERAS
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -194,6 +196,7 @@ SIGNATURES = {
   'ms_photometric_fwd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p, c_void_p]),
   'ms_photometric_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
   'ms_scene_transform': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, POINTER(c_double), c_void_p]),
+  'ms_camera_coverage': (c_int, [c_void_p] * 5 + [c_int, c_double, c_double, c_double, c_int64] + [c_void_p] * 4 + [c_int, c_void_p]),
 }
 
 

@@ -186,6 +186,34 @@ class Gaussians3D(TensorClass):
     return self.replace(position=outs[0], log_scaling=outs[1], rotation=outs[2],
                         feature=outs[3] if with_feature else self.feature)
 
+  def with_filter_3d(self, sigma: torch.Tensor) -> 'Gaussians3D':
+    """The scene with an isotropic 3-D smoothing filter of standard deviation ``sigma`` (n,) baked in, as Mip-Splatting
+    fuses its filter after training (no reference counterpart; ``misc.coverage.Coverage.filter_sigma`` gives the sigma
+    a camera set calls for).  Per axis ``s'^2 = s^2 + sigma^2``; the opacity keeps the gaussian's integral,
+    ``alpha' = alpha sqrt(prod s^2 / prod s'^2)``.  Both are evaluated through the per-axis growth
+    ``s'^2 / s^2 = 1 + (sigma / s)^2``: ``log_scaling' = log_scaling + log1p((sigma / s)^2) / 2`` (a small correction is
+    added to the stored value, not recovered from a logarithm of s'^2), ``alpha'`` from the product of the three
+    ``1 / sqrt(growth)``, stored as ``alpha_logit' = log(alpha') - log1p(-alpha')``.  ``position``, ``rotation`` and ``feature`` are shared with ``self``.
+
+    A plain differentiable torch composition, on purpose: this is an offline operation, and autograd flows to
+    ``log_scaling`` and ``alpha_logit``.  Rows with ``sigma == 0`` keep their ``log_scaling`` and ``alpha_logit`` bitwise
+    (``torch.where`` on the inputs).  Raises ValueError on a ``sigma`` that is not (n,), negative or not finite; that check
+    reads the device."""
+    n = self.position.shape[0]
+    if not isinstance(sigma, torch.Tensor) or tuple(sigma.shape) != (n,):
+      raise ValueError(f"sigma must be a ({n},) tensor, got {tuple(getattr(sigma, 'shape', ()))}")
+    if not sigma.is_floating_point():
+      raise ValueError(f"sigma must be a floating-point tensor, got {sigma.dtype}")
+    if not bool((torch.isfinite(sigma) & (sigma >= 0)).all()):
+      raise ValueError("sigma must be finite and non-negative")
+    sigma = sigma.to(device=self.log_scaling.device, dtype=self.log_scaling.dtype).unsqueeze(1)
+    filtered = sigma > 0
+    ratio = sigma / torch.exp(self.log_scaling)
+    growth = 1 + ratio * ratio                                       # s'^2 / s^2 per axis
+    alpha = torch.sigmoid(self.alpha_logit) * torch.rsqrt(growth).prod(dim=1, keepdim=True)
+    return self.replace(log_scaling=torch.where(filtered, self.log_scaling + 0.5 * torch.log1p(ratio * ratio), self.log_scaling),
+                        alpha_logit=torch.where(filtered, torch.log(alpha) - torch.log1p(-alpha), self.alpha_logit))
+
   @staticmethod
   def concat_batch(gaussians: List['Gaussians3D']) -> 'Gaussians3D':
     return Gaussians3D.cat(gaussians, dim=0)

@@ -10,11 +10,14 @@ gaussians and tile overlaps; ms per frame is the median over the views after one
 --out the images are written as view_000.npy ... (H, W, 3) float32.
 
     python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d] [--transform "x 90 0.5"]
+                                           [--coverage]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 --transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
 similarity matrix) moves the scene after loading, SH bands included (Gaussians3D.transformed, in place); the cameras
 orbit the moved scene.
+--coverage runs camera_coverage over the orbit before rendering and adds to the JSON line the time of the call and how
+many gaussians are seen by no view, by some but not all (1..K-1), and by all K views (the three counts sum to N).
 """
 import argparse
 import json
@@ -29,7 +32,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
-from taichi_splatting_amd import CameraParams, RasterConfig, frame, render_gaussians, scene_io     # noqa: E402
+from taichi_splatting_amd import CameraParams, RasterConfig, camera_coverage, frame, render_gaussians, scene_io     # noqa: E402
 from taichi_splatting_amd.data_types import similarity_from_matrix                                 # noqa: E402
 
 
@@ -77,6 +80,25 @@ def parse_transform(text):
   return m
 
 
+def coverage_report(gaussians, cameras, config):
+  """camera_coverage over ``cameras``: ms of the second call (device events; the first warms up) and the histogram of
+  views per gaussian in three bins"""
+  views = len(cameras)
+  with torch.no_grad():
+    camera_coverage(gaussians, cameras, config)
+    begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    begin.record()
+    cov = camera_coverage(gaussians, cameras, config)
+    end.record()
+    end.synchronize()
+    none, every = int((cov.count == 0).sum()), int((cov.count == views).sum())
+  report = dict(views=views, ms=round(begin.elapsed_time(end), 4), seen_by_none=none,
+                seen_by_some=cov.count.shape[0] - none - every, seen_by_all=every)
+  print(f"coverage: {views} views in {report['ms']:.3f} ms; gaussians seen by 0 / 1..{views - 1} / all {views} views: "
+        f"{none} / {report['seen_by_some']} / {every}", file=sys.stderr, flush=True)
+  return report
+
+
 def main():
   p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
   p.add_argument('scene')
@@ -88,6 +110,8 @@ def main():
   p.add_argument('--transform', default=None, metavar='"AXIS DEG [SCALE]"',
                  help="move the loaded scene: a rotation about x, y or z in degrees and a uniform scale, or 16 numbers "
                       "(row-major 4x4 similarity matrix); SH bands are rotated with it")
+  p.add_argument('--coverage', action='store_true',
+                 help="before rendering, run camera_coverage over the orbit: time, and gaussians seen by 0, 1..K-1, all K views")
   args = p.parse_args()
   try:
     transform = parse_transform(args.transform) if args.transform is not None else None
@@ -118,6 +142,7 @@ def main():
       gaussians.transformed(transform, inplace=True)
   cameras, radius = orbit_cameras(gaussians.position, args.views, tuple(args.size), device)
   config = RasterConfig()
+  coverage = coverage_report(gaussians, cameras, config) if args.coverage else None
 
   visible, overlaps, frame_ms, images = [], [], [], []
   with torch.no_grad():
@@ -144,7 +169,7 @@ def main():
     load_s=round(load_s, 4), read_s=round(timings['read_s'], 4), upload_ms=round(timings['upload_ms'], 3),
     unpack_ms=round(timings['unpack_ms'], 3), visible=visible, overlaps=overlaps,
     frame_ms=round(statistics.median(frame_ms), 4), frame_ms_per_view=[round(ms, 4) for ms in frame_ms],
-    images=str(args.out) if args.out else None)), flush=True)
+    images=str(args.out) if args.out else None, **({'coverage': coverage} if coverage is not None else {}))), flush=True)
 
 
 if __name__ == '__main__':
