@@ -826,6 +826,8 @@ class _FrameFunction(torch.autograd.Function):
     grad_camera = torch.zeros((16,), dtype=dtype, device=device) if need_camera else None
     gr.grad_camera = _lib.ptr(grad_camera)
     if config.compute_point_heuristic:
+      if not moments_path:
+        ctx.heuristic.zero_()     # the generic kernels add; every pass leaves its own heuristics, as the moments path does
       gr.point_heuristic = ctx.heuristic.data_ptr()
     vis_here = state.vis_deferred and moments_path and state.vis_pass is not None
     if vis_here:
@@ -932,6 +934,8 @@ class _RasterizeFrameFunction(torch.autograd.Function):
     if moments_path:
       fixed_exp = attach_moments(gr, g_image, device, n, det)      # noqa: F841 (alive until the launch)
     if heuristic is not None:
+      if not moments_path:
+        heuristic.zero_()         # the generic kernels add; every pass leaves its own heuristics, as the moments path does
       gr.point_heuristic = heuristic.data_ptr()
     _enqueue_backward(state, gr, device, "rasterize backward")
     return (gp if need_points else None), None, (gf if need_features else None), None, None, None, None

@@ -142,6 +142,11 @@ class _RasterFunction(torch.autograd.Function):
     grad_gaussians = alloc(gaussians) if need_points else None
     grad_features = alloc(features) if need_features else None
 
+    if heuristic is not None and not moments_path:
+      # a pass leaves ITS heuristics (INTEGRATION.md difference 19): the finalize pass stores them, the generic kernels
+      # add into the tensor, which a second backward over the same graph (retain_graph) would otherwise double
+      heuristic.zero_()
+
     grad_image = grad_image.contiguous()
     hold = window.placeholder(gaussians.dtype, gaussians.device)
     stream = _lib.current_stream(gaussians.device)
