@@ -197,14 +197,16 @@ int ms_radix_sort_pairs(const void* keys_in, const int32_t* values_in, void* key
                         void* tmp, size_t* tmp_bytes, void* stream);
 
 /* cuda_lib.segmented_sort_pairs (cuda_lib/segmented_sort_pairs.cu:9-73): stable sort of each
- * segment [start_offsets[s], end_offsets[s]) by int32 key, values int32. */
+ * segment [start_offsets[s], end_offsets[s]) by int32 key, values int32.  Segments are disjoint and may be listed
+ * in any order; elements outside every segment (all of them when num_segments == 0) are copied through unchanged. */
 int ms_segmented_sort_pairs(const int32_t* keys_in, const int32_t* values_in, int32_t* keys_out,
                             int32_t* values_out, int64_t n, const int64_t* start_offsets,
                             const int64_t* end_offsets, int64_t num_segments, void* stream);
 
 /* find_ranges_kernel (tile_mapper.py:93-112): out_ranges (num_tiles, 2) int32 = [first, last+1)
  * of each tile id (= key >> tile_shift) in the sorted key list; empty tiles get [0, 0).  The
- * function zero-fills out_ranges itself. */
+ * function zero-fills out_ranges itself.  0 <= tile_shift <= 8 key_bytes (the whole width: every key is tile 0); ids
+ * >= num_tiles are ignored. */
 int ms_find_ranges(const void* sorted_keys, int64_t k, int key_bytes, int tile_shift,
                    int64_t num_tiles, int32_t* out_ranges, void* stream);
 

@@ -676,8 +676,10 @@ find_ranges_kernel(const KeyT* __restrict__ keys, int64_t k, const int32_t* __re
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k_dev) k = *k_dev;
   if (i >= k) return;
-  const int64_t tile = (int64_t)(keys[i] >> shift);
-  const int64_t next = (i + 1 < k) ? (int64_t)(keys[i + 1] >> shift) : -1;
+  // a shift by the key's whole width leaves tile 0 (the shift instruction itself would take the count modulo the width)
+  const bool whole = shift >= (int)(8 * sizeof(KeyT));
+  const int64_t tile = whole ? 0 : (int64_t)(keys[i] >> shift);
+  const int64_t next = (i + 1 < k) ? (whole ? 0 : (int64_t)(keys[i + 1] >> shift)) : -1;
   if (i == 0 && tile < num_tiles) ranges[tile * 2 + 0] = 0;
   if (tile != next) {
     if (tile < num_tiles) ranges[tile * 2 + 1] = (int32_t)(i + 1);
@@ -854,13 +856,16 @@ extern "C" int ms_segmented_sort_pairs(const int32_t* keys_in, const int32_t* va
                                        int32_t* values_out, int64_t n, const int64_t* start_offsets,
                                        const int64_t* end_offsets, int64_t num_segments, void* stream) {
   MS_CHECK_ARG(n >= 0 && num_segments >= 0, "negative size");
-  if (n == 0 || num_segments == 0) return 0;
-  MS_CHECK_ARG(keys_in && values_in && keys_out && values_out && start_offsets && end_offsets, "null pointer");
-  // elements outside every segment are copied through unchanged (CUB leaves them unspecified)
+  if (n == 0) return 0;
+  MS_CHECK_ARG(keys_in && values_in && keys_out && values_out, "null pointer");
+  MS_CHECK_ARG(num_segments == 0 || (start_offsets && end_offsets), "null segment offsets");
+  // elements outside every segment are copied through unchanged (CUB leaves them unspecified): all of them when
+  // there is no segment
   copy_pairs_kernel<int32_t><<<dim3((unsigned)div_up(n, 256)), dim3(256), 0, (hipStream_t)stream>>>(
       keys_in, values_in, keys_out, values_out, n);
-  segmented_rank_sort_kernel<<<dim3((unsigned)num_segments), dim3(256), 0, (hipStream_t)stream>>>(
-      keys_in, values_in, keys_out, values_out, start_offsets, end_offsets);
+  if (num_segments > 0)
+    segmented_rank_sort_kernel<<<dim3((unsigned)num_segments), dim3(256), 0, (hipStream_t)stream>>>(
+        keys_in, values_in, keys_out, values_out, start_offsets, end_offsets);
   MS_CHECK_LAUNCH();
   return 0;
 }
@@ -869,6 +874,7 @@ extern "C" int ms_find_ranges(const void* sorted_keys, int64_t k, int key_bytes,
                               int64_t num_tiles, int32_t* out_ranges, void* stream) {
   MS_CHECK_ARG(k >= 0 && num_tiles >= 0, "negative size");
   MS_CHECK_ARG(key_bytes == 4 || key_bytes == 8, "key_bytes must be 4 or 8");
+  MS_CHECK_ARG(tile_shift >= 0 && tile_shift <= key_bytes * 8, "tile_shift outside the key");
   MS_CHECK_ARG(out_ranges != nullptr || num_tiles == 0, "out_ranges is null");
   if (num_tiles > 0)
     MS_CHECK_HIP(hipMemsetAsync(out_ranges, 0, (size_t)num_tiles * 2 * sizeof(int32_t), (hipStream_t)stream));
