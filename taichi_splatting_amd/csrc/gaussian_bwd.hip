@@ -45,7 +45,56 @@ template <typename T> struct GaussBwdDev {
   const T *camera_position, *colours;
   T *grad_position, *grad_log_scaling, *grad_rotation, *grad_alpha_logit, *grad_feature, *grad_camera;
   T *store_points7, *store_colours, *point_heuristic, *point_visibility;
+  int stage_inputs;               // moment-row kernels: full blocks of 64 gaussians arrive through LDS (stage_geometry)
 };
+
+// One wave's block of 64 gaussians, as the LDS-DMA loads of stage_geometry / stage_rows lay it down: lane l's piece
+// of a load lands at l x 4 bytes behind the load's base for a 4-byte piece and at l x 16 bytes for a 12- or 16-byte
+// one (a 12-byte piece leaves the fourth word of its slot alone: measured on MI355X), so gaussian j's values sit where
+// lane j reads them.  Offsets in floats; every array but depth and alpha logit has four floats per gaussian.
+constexpr int GB_ST_DEPTH = 0, GB_ST_ALPHA = 64, GB_ST_POS = 128, GB_ST_LS = 384, GB_ST_COL = 640, GB_ST_ROT = 896,
+              GB_ST_MOM = 1152;
+constexpr int GB_ST_FLOATS = GB_ST_MOM;              // fixed-point rows keep their own whole-line path
+constexpr int GB_ST_FLOATS_MOM = GB_ST_MOM + 64 * 12;
+
+// (the piece size has to be a literal for the builtin) src: per lane; dst: the wave's, where lane 0's piece lands
+#define MS_LDS_DMA(src, dst, BYTES)                                                                   \
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),             \
+                                   (__attribute__((address_space(3))) void*)(dst), BYTES, 0, 0)
+
+// A block that is not staged loads its inputs as lanes always did, on a path of its own beside the staged one.  Where
+// the two meet the compiler would wait for "everything in flight", which on the staged path is the next block's DMA:
+// the loaded values are waited for on their own path (an empty statement that takes them as operands does that),
+// which also keeps the two paths from being merged into one load through a generic pointer.
+__device__ __forceinline__ void landed(float& v) { asm volatile("" : "+v"(v)); }
+template <typename... V>
+__device__ __forceinline__ void landed(float& v, V&... more) { landed(v); landed(more...); }
+
+// Sends for the 64 gaussians from `base` on (all of them < n: the caller checks) into the wave's staging rows.  No
+// register holds the data on its way, so a wave issues this for its NEXT block in the middle of the current one.
+__device__ __forceinline__ void stage_geometry(const GaussBwdDev<float>& a, int64_t base, int lane, float* st) {
+  const int64_t i = base + lane;
+  MS_LDS_DMA(a.depth + i, st + GB_ST_DEPTH, 4);
+  MS_LDS_DMA(a.alpha_logit + i, st + GB_ST_ALPHA, 4);
+  MS_LDS_DMA(a.position + i * 3, st + GB_ST_POS, 12);
+  MS_LDS_DMA(a.log_scaling + i * 3, st + GB_ST_LS, 12);
+  MS_LDS_DMA(a.rotation + i * 4, st + GB_ST_ROT, 16);
+}
+
+// the arrays a block reads last: forward colours and, ROWS, the moment rows
+template <bool ROWS>
+__device__ __forceinline__ void stage_rows(const GaussBwdDev<float>& a, int64_t base, int lane, float* st) {
+  MS_LDS_DMA(a.colours + (base + lane) * 3, st + GB_ST_COL, 12);
+  if constexpr (ROWS) {
+    // the three used quarters of each 64-byte row: piece t * 64 + lane is quarter (piece % 3) of row (piece / 3)
+    const float* rows = reinterpret_cast<const float*>(a.moments) + base * MS_MOMENT_ROW;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int piece = t * 64 + lane, j = piece / 3, k = piece - j * 3;
+      MS_LDS_DMA(rows + j * MS_MOMENT_ROW + k * 4, st + GB_ST_MOM + t * 256, 16);
+    }
+  }
+}
 
 // MOM: the 2D-boundary gradients come from the moment rows (float32, RGB); FIXED: rows of 64-bit fixed point.
 // DEG >= 0: d(colour) -> d(SH parameters); DEG == -1: plain colours (grad_feature (n, 3) from the moment rows only —
@@ -67,6 +116,14 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
   // into floats on the way and handed to their lanes through LDS (round 5; a lane walking its own row with twelve
   // 8-byte loads and stores made this pass 0.43 -> 1.16 ms on config D)
   __shared__ float4 s_mom[(MOM && FIXED) ? 4 : 1][(MOM && FIXED) ? 64 * 3 : 1];
+  // STAGE: the kernels the frame executor launches on moment rows (every stored band active) bring full blocks in by
+  // LDS-DMA: all of a block's loads are in flight at once and hold no register on the way (read lane by lane, the
+  // block made four dependent trips to memory: 0.48 -> 0.43 ms on config D, profiles/gaussian_bwd_pipeline.txt).  Where
+  // the grid-stride loop runs on (grad_camera caps the grid), the loads of block b + 1 are issued in the middle of
+  // block b, each array's as soon as block b has taken its values: one buffer per wave is enough.
+  constexpr bool STAGE = MOM && !STRIDED && DEG >= 0 && sizeof(T) == 4;
+  constexpr int ST_FLOATS = !STAGE ? 4 : FIXED ? GB_ST_FLOATS : GB_ST_FLOATS_MOM;
+  __shared__ __attribute__((aligned(16))) float s_stage[STAGE ? 4 : 1][ST_FLOATS];
 
   const int wave = threadIdx.x >> 6, lane = lane_id();
   T cam_grad[16];
@@ -91,12 +148,45 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
     asm volatile("" : "+v"(pp.width), "+v"(pp.height), "+v"(pp.blur_cov), "+v"(pp.clamp_margin), "+v"(pp.alpha_threshold));
   }
 
+  // block-invariant: loaded once, not once per block
+  T campos[3] = {T(0), T(0), T(0)};
+  if constexpr (DEG >= 0) { campos[0] = a.camera_position[0]; campos[1] = a.camera_position[1]; campos[2] = a.camera_position[2]; }
+  double s_main = 0.0, s_h0 = 0.0;
+  if constexpr (MOM && FIXED) { s_main = ldexp(1.0, -a.fixed_exp[0]); s_h0 = ldexp(1.0, -a.fixed_exp[1]); }
+
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  int64_t base = ((int64_t)blockIdx.x * 4 + wave) * 64;
+  bool staged = false;             // this block's inputs are in (or on their way into) s_stage[wave]
+  if constexpr (STAGE) {
+    staged = a.stage_inputs && base + 64 <= a.n;
+    if (staged) { stage_geometry(a, base, lane, s_stage[wave]); stage_rows<!FIXED>(a, base, lane, s_stage[wave]); }
+  }
   // a wave takes 64 consecutive gaussians per iteration (the SH rows of a wave leave as coalesced stores)
-  for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * 64; base < a.n; base += (int64_t)gridDim.x * 256) {
+  bool next_staged = false;
+  for (; base < a.n; base += stride, staged = next_staged) {
     const int64_t i = base + lane;
     const int count = (a.n - base) < 64 ? (int)(a.n - base) : 64;
     const bool valid = lane < count;
-    const bool vis = valid && a.depth[i] > T(0);
+    // the block's inputs: from the staging rows (a full block, every lane has a row), or, for the ragged last block
+    // and for arrays the DMA cannot take, by the lane's own loads.  Taken OUTSIDE the divergent parts: the next block's
+    // DMA needs every lane, and is issued as soon as the rows are free.
+    T depth_i = T(0), al = T(0), p[3] = {T(0), T(0), T(0)}, ls[3] = {T(0), T(0), T(0)}, q[4] = {T(0), T(0), T(0), T(0)};
+    if constexpr (STAGE) {
+      if (staged) {
+        const float* st = s_stage[wave];
+        depth_i = st[GB_ST_DEPTH + lane]; al = st[GB_ST_ALPHA + lane];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p[k] = st[GB_ST_POS + lane * 4 + k]; ls[k] = st[GB_ST_LS + lane * 4 + k]; }
+        const float4 qv = *reinterpret_cast<const float4*>(st + GB_ST_ROT + lane * 4);
+        q[0] = qv.x; q[1] = qv.y; q[2] = qv.z; q[3] = qv.w;
+      } else if (valid) {
+        depth_i = a.depth[i];
+        landed(depth_i);
+      }
+      next_staged = a.stage_inputs && base + stride + 64 <= a.n;
+    }
+    if constexpr (!STAGE) { if (valid) depth_i = a.depth[i]; }
+    const bool vis = valid && depth_i > T(0);
 
     T gp[7] = {T(0), T(0), T(0), T(0), T(0), T(0), T(0)};
     T gcov[3] = {T(0), T(0), T(0)};          // MOM: dL/d(a, b, c) of the 2D covariance straight from the moments
@@ -107,7 +197,6 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
     if constexpr (MOM && FIXED) {
       struct alignas(16) Pair { long long lo, hi; };
       Pair* blk = reinterpret_cast<Pair*>(reinterpret_cast<long long*>(a.moments) + base * MS_MOMENT_ROW);
-      const double s_main = ldexp(1.0, -a.fixed_exp[0]), s_h0 = ldexp(1.0, -a.fixed_exp[1]);
       float* flat = reinterpret_cast<float*>(&s_mom[wave][0]);
       wave_lds_fence();
       // (two rounds of four loads in flight: eight kept 32 registers busy and the kernel at 172 VGPRs = two waves per
@@ -127,12 +216,25 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
       }
       wave_lds_fence();
     }
+    if constexpr (STAGE) {
+      // the geometry is in registers: its rows are free for the next block's, which have this whole block to land in
+      // (behind the fixed-point rows' own loads, whose wait would otherwise be a wait for this DMA as well)
+      if (next_staged) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads returned before a DMA write can arrive
+        stage_geometry(a, base + stride, lane, s_stage[wave]);
+      }
+    }
     if (vis) {
-      const T p[3] = {a.position[i * 3 + 0], a.position[i * 3 + 1], a.position[i * 3 + 2]};
-      const T ls[3] = {a.log_scaling[i * 3 + 0], a.log_scaling[i * 3 + 1], a.log_scaling[i * 3 + 2]};
-      const T q[4] = {a.rotation[i * 4 + 0], a.rotation[i * 4 + 1], a.rotation[i * 4 + 2], a.rotation[i * 4 + 3]};
+      if (!staged) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p[k] = a.position[i * 3 + k]; ls[k] = a.log_scaling[i * 3 + k]; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = a.rotation[i * 4 + k];
+        al = a.alpha_logit[i];
+        if constexpr (STAGE) { landed(p[0], p[1], p[2]); landed(ls[0], ls[1], ls[2]); landed(q[0], q[1], q[2], q[3]); landed(al); }
+      }
       ProjState<T> st;
-      project_forward(p, ls, q, a.alpha_logit[i], cam, pp, st);
+      project_forward(p, ls, q, al, cam, pp, st);
 
       if constexpr (MOM) {
         // moments -> gradients of the packed 2D gaussian and its colour (raster_bwd_scan.hip, generic.py:321-336);
@@ -142,7 +244,14 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
           r0 = s_mom[wave][lane * 3 + 0]; r1 = s_mom[wave][lane * 3 + 1]; r2 = s_mom[wave][lane * 3 + 2];
         } else {
           float4* row = reinterpret_cast<float4*>(reinterpret_cast<float*>(a.moments) + i * MS_MOMENT_ROW);
-          r0 = row[0]; r1 = row[1]; r2 = row[2];
+          // a staged row was read from LDS behind the wait for its DMA: it has landed, the zeros may go out
+          if (staged) {
+            const float4* mom = reinterpret_cast<const float4*>(&s_stage[wave][GB_ST_MOM]);
+            r0 = mom[lane * 3 + 0]; r1 = mom[lane * 3 + 1]; r2 = mom[lane * 3 + 2];
+          } else {
+            r0 = row[0]; r1 = row[1]; r2 = row[2];
+            if constexpr (STAGE) { landed(r0.x, r0.y, r0.z, r0.w); landed(r1.x, r1.y, r1.z, r1.w); landed(r2.x, r2.y, r2.z, r2.w); }
+          }
           const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
           row[0] = z; row[1] = z; row[2] = z;
         }
@@ -219,7 +328,7 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
       }
 
       if constexpr (DEG >= 0) {
-        const T dx = p[0] - a.camera_position[0], dy = p[1] - a.camera_position[1], dz = p[2] - a.camera_position[2];
+        const T dx = p[0] - campos[0], dy = p[1] - campos[1], dz = p[2] - campos[2];
         const T len = t_sqrt(dx * dx + dy * dy + dz * dz);
         T Y[YW];
 #pragma unroll
@@ -228,10 +337,15 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
 #pragma unroll
         for (int d = 0; d < YW; ++d) s_Y[wave][lane * YS + d] = Y[d];
         // the clamp passes the gradient strictly inside (0, 1) (sh.hip)
-        _Pragma("unroll") for (int c = 0; c < GB_MAX_F; ++c) if (c < a.f) {
-          const T o = a.colours[i * a.f + c];
-          s_g[wave][lane * GB_MAX_F + c] = (o > T(0) && o < T(1)) ? gf[c] : T(0);
+        T o[GB_MAX_F] = {T(0), T(0), T(0), T(0)};
+        if (staged) {
+          _Pragma("unroll") for (int c = 0; c < 3; ++c) o[c] = (T)s_stage[wave][GB_ST_COL + lane * 4 + c];
+        } else {
+          _Pragma("unroll") for (int c = 0; c < GB_MAX_F; ++c) if (c < a.f) o[c] = a.colours[i * a.f + c];
+          if constexpr (STAGE) landed(o[0], o[1], o[2]);
         }
+        _Pragma("unroll") for (int c = 0; c < GB_MAX_F; ++c) if (c < a.f)
+          s_g[wave][lane * GB_MAX_F + c] = (o[c] > T(0) && o[c] < T(1)) ? gf[c] : T(0);
       }
     } else if (valid) {
       if constexpr (DEG >= 0) {
@@ -241,6 +355,13 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
       }
     }
 
+    if constexpr (STAGE) {
+      // moment rows and colours were the last staged values taken: the next block's go out ahead of this one's stores
+      if (next_staged) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        stage_rows<!FIXED>(a, base + stride, lane, s_stage[wave]);
+      }
+    }
     if (valid) {
       if (a.grad_position) {
 #pragma unroll
@@ -306,8 +427,10 @@ __device__ __forceinline__ void gaussian_bwd_body(const GaussBwdDev<T>& a, int s
   if (a.grad_camera) block_sum_commit<T, 16>(cam_grad, a.grad_camera, s_cam);
 }
 
+// (the staging kernels are told to fit three waves per SIMD, which their LDS allows: left to itself the register
+// allocator settles a few registers above the 168 that takes)
 template <typename T, int DEG, bool MOM, bool FIXED>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MOM && DEG >= 0 && sizeof(T) == 4 ? 3 : 1)))
 gaussian_bwd_kernel(const GaussBwdDev<T> a) {
   gaussian_bwd_body<T, DEG, MOM, FIXED, false>(a, 0);
 }
@@ -343,10 +466,21 @@ static int launch_typed(const GaussianBwdArgs& g, hipStream_t s) {
   a.store_points7 = (T*)g.store_points7; a.store_colours = (T*)g.store_colours; a.point_heuristic = (T*)g.point_heuristic;
   a.point_visibility = (T*)g.point_visibility;
 
+  const bool mom = g.moments != nullptr;
   int64_t blocks = div_up(g.n, 256);
+  a.stage_inputs = 0;
+  if constexpr (sizeof(T) == 4) {
+    if (mom) {
+      // 16-byte DMA pieces want 16-byte aligned sources (a caller's tensor may be a view at any multiple of 4), the
+      // 4- and 12-byte ones only the alignment of a float
+      a.stage_inputs = ((reinterpret_cast<uintptr_t>(g.rotation) | reinterpret_cast<uintptr_t>(g.moments)) & 15) == 0 &&
+                       ((reinterpret_cast<uintptr_t>(g.position) | reinterpret_cast<uintptr_t>(g.log_scaling) |
+                         reinterpret_cast<uintptr_t>(g.alpha_logit) | reinterpret_cast<uintptr_t>(g.depth) |
+                         reinterpret_cast<uintptr_t>(g.colours)) & 3) == 0;
+    }
+  }
   if (g.grad_camera && blocks > 2048) blocks = 2048;      // bounded atomic count for the 16 camera sums
   const dim3 grid((unsigned)blocks), block(256);
-  const bool mom = g.moments != nullptr;
   // fewer active bands than stored ones: the *_active_kernel of the active degree, the stored row length at run time
   const int active = g.sh_active_bands > 0 && g.sh_active_bands <= g.sh_degree ? g.sh_active_bands - 1 : g.sh_degree;
   const int stored_d = (g.sh_degree + 1) * (g.sh_degree + 1);
