@@ -817,6 +817,73 @@ int ms_camera_coverage(const void* position, const void* log_scaling, const void
                        double alpha_threshold, int64_t n, int32_t* out_count, void* out_max_rate, void* out_min_depth,
                        uint32_t* out_mask /* may be NULL */, int dtype, void* stream);
 
+/* ---- Fixed-budget densification: relocate dead gaussians, perturb positions (csrc/relocate.hip) -----------------------
+ * An addition with no reference counterpart: the strategy of 3DGS-MCMC (Kheradmand et al., "3D Gaussian Splatting as
+ * Markov Chain Monte Carlo", NeurIPS 2024).  The row count never changes and every array keeps its storage; no call
+ * allocates, synchronises or reads device memory from the host, so the whole step can be captured into a graph.
+ * All float arrays are float32; n < 2^30.  The calls of one step, in order, on one stream:
+ *
+ * ms_relocate_weights: row i is dead iff !(alpha_logit[i] > threshold) (NaN is dead); threshold is
+ *   float32(logit(min_opacity)), computed by the caller in double.  weights[i] (int64) = 0 for a dead row, else
+ *   max(1, llrint(sigmoid(alpha_logit[i]) 2^24)) evaluated in double.  Also clears count (n int32) and counts (3 int64)
+ *   for the calls below.
+ * The caller then forms cdf = the inclusive int64 sum of weights (exact, whatever the order of the additions).
+ * ms_relocate_draw: random is n 64-bit words read as unsigned.  With total = cdf[n - 1] > 0 a dead row i takes
+ *   target = (random[i] * total) >> 64, src[i] = the first j with cdf[j] > target (a live row) and adds 1 to count[j];
+ *   a live row gets src[i] = i.  With total == 0 (every row dead) every row gets src[i] = i and nothing will move.
+ *   counts[0] = number of dead rows, counts[2] = total.
+ * ms_relocate_fresh: for every row j with count[j] > 0, in double from the float32 inputs, rounded once:
+ *     ratio = min(count[j] + 1, MS_RELOCATE_MAX_RATIO)    o = sigmoid(alpha_logit[j])    o' = 1 - (1 - o)^(1 / ratio)
+ *     denom = sum_{i = 1 .. ratio} sum_{k = 0 .. i - 1} C(i - 1, k) (-1)^k o'^(k + 1) / sqrt(k + 1)    coeff = o / denom
+ *     fresh_opacity[j] = logit(clamp(o', min_opacity, 1 - 1e-7))
+ *     fresh_scale[j, d] = log_scaling[j, d] + ln(coeff)      for d < scale_dims (1 .. 16)
+ *   binomials: DEVICE array of MS_RELOCATE_MAX_RATIO^2 doubles, row-major, [m][k] = C(m, k) (0 for k > m).  Rows that were
+ *   not drawn are not written.  counts[1] = number of drawn rows.
+ * ms_relocate_move: every array of the scene in ONE launch, IN PLACE.  A row is touched if it is dead and moves
+ *   (src[i] != i) or live and drawn (count[i] > 0); an untouched row is neither read nor written.  By role:
+ *     MS_RELOCATE_COPY          a moved row takes row src[i] of the same array; a drawn row keeps its own
+ *     MS_RELOCATE_ZERO_TOUCHED  moved and drawn rows become zero (optimiser moments)
+ *     MS_RELOCATE_INHERIT       as MS_RELOCATE_COPY (state that follows the gaussian, e.g. a running visibility)
+ *     MS_RELOCATE_OPACITY / MS_RELOCATE_SCALE   moved and drawn rows take row src[i] of `fresh`, a side buffer with the
+ *                               array's row layout written by ms_relocate_fresh: a source's new values are never read
+ *                               from the array that is being written
+ *   Sources are live and destinations dead, so the copies of one array never overlap.  Rows move as 16-byte pieces when
+ *   row_bytes % 16 == 0 and the bases are 16-byte aligned, as 4-byte pieces otherwise; row_bytes must be a positive
+ *   multiple of 4 (at most 1 MiB).  Every descriptor is checked before the first launch.  `arrays` is a HOST array.
+ * MS_ERR_BAD_ARG: n outside [0, 2^30), a NULL or misaligned pointer, scale_dims outside 1..16, min_opacity outside
+ * (0, 1 - 1e-7), NaN threshold, an unknown role, fresh == data; MS_ERR_ABI: a descriptor of another size. */
+#define MS_RELOCATE_MAX_RATIO 51
+enum { MS_RELOCATE_COPY = 0, MS_RELOCATE_ZERO_TOUCHED = 1, MS_RELOCATE_INHERIT = 2, MS_RELOCATE_OPACITY = 3,
+       MS_RELOCATE_SCALE = 4 };
+typedef struct ms_relocate_array {
+  uint32_t struct_size;            /* sizeof(ms_relocate_array) */
+  int32_t role;                    /* MS_RELOCATE_* */
+  void* data;                      /* (n, row_bytes), modified in place */
+  const void* fresh;               /* (n, row_bytes) side buffer of the OPACITY / SCALE roles, ignored otherwise */
+  int64_t row_bytes;
+} ms_relocate_array;
+int ms_relocate_weights(const float* alpha_logit, int64_t n, float threshold, int64_t* weights, int32_t* count,
+                        int64_t* counts, void* stream);
+int ms_relocate_draw(const int64_t* weights, const int64_t* cdf, const uint64_t* random, int64_t n, int32_t* src,
+                     int32_t* count, int64_t* counts, void* stream);
+int ms_relocate_fresh(const float* alpha_logit, const float* log_scaling, int scale_dims, const int32_t* count, int64_t n,
+                      double min_opacity, const double* binomials, float* fresh_opacity, float* fresh_scale,
+                      int64_t* counts, void* stream);
+int ms_relocate_move(const ms_relocate_array* arrays, int num_arrays, const int32_t* src, const int32_t* count, int64_t n,
+                     void* stream);
+
+/* ms_perturb_positions: the exploration noise of the same paper, one lane per gaussian, in place on position (n, 3):
+ *   position += step g(o) Sigma z      Sigma = R diag(exp(2 log_scaling)) R^T      o = sigmoid(alpha_logit)
+ *   g(o) = 1 / (1 + exp(-k ((1 - o) - x0)))          (the paper: k = 100, x0 = 0.995)
+ * R is the rotation of the xyzw quaternion normalised as in the projection; z (n, 3) is drawn by the caller.  step g is
+ * evaluated in double (k amplifies a float32 rounding of 1 - o a hundredfold, and g of an opaque gaussian lies below the
+ * float32 normal range), Sigma z in float32, their product is rounded to float32 once.  A row whose
+ * step g(o) is exactly zero, whose offset is zero, or whose quaternion is zero or not finite keeps its position bit
+ * for bit.  With position, log_scaling, rotation and z 16-byte aligned every access is 16 bytes wide, else 4.
+ * MS_ERR_BAD_ARG: n outside [0, 2^31), a NULL or misaligned pointer, a NaN step, k or x0. */
+int ms_perturb_positions(float* position, const float* log_scaling, const float* rotation, const float* alpha_logit,
+                         const float* z, int64_t n, float step, double k, double x0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

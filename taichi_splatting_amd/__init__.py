@@ -20,6 +20,8 @@ from .taichi_queue import TaichiQueue, taichi_queue, queued
 from .loss import l1_ssim_loss, ssim
 from .scene_io import load_ply, save_ply, read_ply_header
 from .misc.coverage import camera_coverage, pack_cameras, Coverage
+from .misc.relocate import relocate_gaussians3d, perturb_positions
+from .optim.relocate import relocate, RelocateResult
 
 __version__ = '0.5.0'       # = MS_VERSION 500 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -33,6 +35,7 @@ __all__ = [
   'l1_ssim_loss', 'ssim',
   'load_ply', 'save_ply', 'read_ply_header',
   'camera_coverage', 'pack_cameras', 'Coverage',
+  'relocate', 'RelocateResult', 'relocate_gaussians3d', 'perturb_positions',
 ]
 
 
@@ -45,7 +48,7 @@ def install_as_taichi_splatting():
   for sub in ('data_types', 'scene_io', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
-              'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'optim', 'optim.fractional',
+              'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'optim', 'optim.fractional', 'optim.relocate',
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',

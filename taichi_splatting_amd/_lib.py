@@ -32,6 +32,8 @@ SCENE_XFORM_ROWS = 256     # MS_SCENE_XFORM_ROWS: rows per workgroup of ms_scene
 SCENE_XFORM_VALUES = 100   # MS_SCENE_XFORM_VALUES: doubles of its host transform array
 COVERAGE_CAMERA_VALUES = 20     # MS_COVERAGE_CAMERA_VALUES: values per camera row of ms_camera_coverage
 COVERAGE_MAX_CAMERAS = 65535    # MS_COVERAGE_MAX_CAMERAS
+RELOCATE_MAX_RATIO = 51         # MS_RELOCATE_MAX_RATIO: side of the binomial table of ms_relocate_fresh
+RELOCATE_COPY, RELOCATE_ZERO_TOUCHED, RELOCATE_INHERIT, RELOCATE_OPACITY, RELOCATE_SCALE = range(5)   # MS_RELOCATE_*
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -133,6 +135,14 @@ class DensifyArrayC(ctypes.Structure):
   ]
 
 
+class RelocateArrayC(ctypes.Structure):
+  """``ms_relocate_array``"""
+  _fields_ = [
+    ('struct_size', ctypes.c_uint32), ('role', c_int32),
+    ('data', c_void_p), ('fresh', c_void_p), ('row_bytes', c_int64),
+  ]
+
+
 # name -> (restype, argtypes); must list every function declared in include/mi355_splat.h
 SIGNATURES = {
   'ms_version': (c_int, []),
@@ -197,6 +207,11 @@ SIGNATURES = {
   'ms_photometric_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
   'ms_scene_transform': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, POINTER(c_double), c_void_p]),
   'ms_camera_coverage': (c_int, [c_void_p] * 5 + [c_int, c_double, c_double, c_double, c_int64] + [c_void_p] * 4 + [c_int, c_void_p]),
+  'ms_relocate_weights': (c_int, [c_void_p, c_int64, c_float] + [c_void_p] * 4),
+  'ms_relocate_draw': (c_int, [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
+  'ms_relocate_fresh': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_double] + [c_void_p] * 5),
+  'ms_relocate_move': (c_int, [POINTER(RelocateArrayC), c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+  'ms_perturb_positions': (c_int, [c_void_p] * 5 + [c_int64, c_float, c_double, c_double, c_void_p]),
 }
 
 

@@ -1,4 +1,6 @@
 from .knn import knn, mean_knn_dist2
 from .coverage import camera_coverage, pack_cameras, Coverage
+from .relocate import relocate_gaussians3d, perturb_positions
 
-__all__ = ["knn", "mean_knn_dist2", "camera_coverage", "pack_cameras", "Coverage"]
+__all__ = ["knn", "mean_knn_dist2", "camera_coverage", "pack_cameras", "Coverage", "relocate_gaussians3d",
+           "perturb_positions"]

@@ -199,3 +199,9 @@ class ParameterClass:
     (``optim/densify.py``: one host read, one move launch for all tensors and state tensors)."""
     from .densify import densify
     return densify(self, prune_mask, split_mask, children, **kwargs)
+
+  def relocate(self, **kwargs):
+    """Fixed-budget densification, in place: dead rows move onto live rows drawn by opacity, the row count, the storage
+    and the optimiser stay (``optim/relocate.py``: no host read, capturable into a graph)."""
+    from .relocate import relocate
+    return relocate(self, **kwargs)
