@@ -884,6 +884,32 @@ int ms_relocate_move(const ms_relocate_array* arrays, int num_arrays, const int3
 int ms_perturb_positions(float* position, const float* log_scaling, const float* rotation, const float* alpha_logit,
                          const float* z, int64_t n, float step, double k, double x0, void* stream);
 
+/* ---- k-means over (N, D) float32 rows: the two halves of a Lloyd iteration (no reference counterpart) ----
+ * 1 <= d <= MS_KMEANS_MAX_D, 1 <= k <= MS_KMEANS_MAX_K, 0 <= n < 2^31 - 1024.  Both calls: tmp == NULL returns
+ * *tmp_bytes for (n, d, k); no host read, allocation, synchronisation or atomic, so they capture into a graph and two
+ * runs are bitwise equal.  MS_ERR_BAD_ARG names the argument; MS_ERR_TMP_TOO_SMALL a short *tmp_bytes.
+ *
+ * ms_kmeans_assign: out_index[i] = argmin_j s(i, j), s(i, j) = ||c_j||^2 - 2 x_i . c_j evaluated on the exact
+ * f32-input MFMA as the fmaf chain that starts at ||c_j||^2 (a float64 sum rounded once) and adds -2 x_ik c_jk for
+ * k = 0..d-1 in order; the lowest index wins a tie.  out_dist2[i] (may be NULL) = max(s_best + ||x_i||^2, 0) with
+ * ||x_i||^2 a float64 sum rounded once.  A workgroup stages MS_KMEANS_CHUNK codes per pass.  x and codebook must be
+ * finite (a NaN or infinity gives an unspecified index in 0..k-1, no stray access).  n == 0 launches nothing.
+ *
+ * ms_kmeans_update: codebook[j] = sum_i w_i x_i / sum_i w_i over index[i] == j, in place; weights (N,) >= 0 or NULL
+ * (all 1).  float64 accumulation in an order fixed by (n, index): pairs sorted by code with ms_radix_sort_pairs, runs
+ * cut into MS_KMEANS_UPDATE_CHUNK entries, chunks combined in list order.  A code with no member or zero weight keeps
+ * its row bit for bit.  out_counts (k,) = members per code; out_weight_sums (k,) float64 may be NULL.  An index outside
+ * 0..k-1 is clamped (wrong result, no stray access). */
+#define MS_KMEANS_MAX_D 64
+#define MS_KMEANS_MAX_K 65536
+#define MS_KMEANS_CHUNK 128
+#define MS_KMEANS_UPDATE_CHUNK 1024
+int ms_kmeans_assign(const float* x, int64_t n, int d, const float* codebook, int k, int32_t* out_index,
+                     float* out_dist2 /* may be NULL */, void* tmp, size_t* tmp_bytes, void* stream);
+int ms_kmeans_update(const float* x, const int32_t* index, const float* weights /* may be NULL */, int64_t n, int d,
+                     int k, float* codebook, int32_t* out_counts, double* out_weight_sums /* may be NULL */, void* tmp,
+                     size_t* tmp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ from .scene_io import load_ply, save_ply, read_ply_header
 from .misc.coverage import camera_coverage, pack_cameras, Coverage
 from .misc.relocate import relocate_gaussians3d, perturb_positions
 from .optim.relocate import relocate, RelocateResult
+from .misc.kmeans import kmeans, kmeans_assign, kmeans_update, KMeansResult
+from .scene_codec import compress_scene, load_compressed, CompressedScene
 
 __version__ = '0.5.0'       # = MS_VERSION 500 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -36,6 +38,8 @@ __all__ = [
   'load_ply', 'save_ply', 'read_ply_header',
   'camera_coverage', 'pack_cameras', 'Coverage',
   'relocate', 'RelocateResult', 'relocate_gaussians3d', 'perturb_positions',
+  'kmeans', 'kmeans_assign', 'kmeans_update', 'KMeansResult',
+  'compress_scene', 'load_compressed', 'CompressedScene',
 ]
 
 
@@ -48,7 +52,7 @@ def install_as_taichi_splatting():
   for sub in ('data_types', 'scene_io', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
-              'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'optim', 'optim.fractional', 'optim.relocate',
+              'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'optim', 'optim.fractional', 'optim.relocate',
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',

@@ -33,6 +33,9 @@ SCENE_XFORM_VALUES = 100   # MS_SCENE_XFORM_VALUES: doubles of its host transfor
 COVERAGE_CAMERA_VALUES = 20     # MS_COVERAGE_CAMERA_VALUES: values per camera row of ms_camera_coverage
 COVERAGE_MAX_CAMERAS = 65535    # MS_COVERAGE_MAX_CAMERAS
 RELOCATE_MAX_RATIO = 51         # MS_RELOCATE_MAX_RATIO: side of the binomial table of ms_relocate_fresh
+KMEANS_MAX_D, KMEANS_MAX_K = 64, 65536   # MS_KMEANS_MAX_D / MS_KMEANS_MAX_K
+KMEANS_CHUNK = 128              # MS_KMEANS_CHUNK: codes a workgroup of ms_kmeans_assign stages per pass
+KMEANS_UPDATE_CHUNK = 1024      # MS_KMEANS_UPDATE_CHUNK: sorted entries per workgroup of ms_kmeans_update
 RELOCATE_COPY, RELOCATE_ZERO_TOUCHED, RELOCATE_INHERIT, RELOCATE_OPACITY, RELOCATE_SCALE = range(5)   # MS_RELOCATE_*
 
 _lib: Optional[ctypes.CDLL] = None
@@ -212,6 +215,8 @@ SIGNATURES = {
   'ms_relocate_fresh': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_double] + [c_void_p] * 5),
   'ms_relocate_move': (c_int, [POINTER(RelocateArrayC), c_int, c_void_p, c_void_p, c_int64, c_void_p]),
   'ms_perturb_positions': (c_int, [c_void_p] * 5 + [c_int64, c_float, c_double, c_double, c_void_p]),
+  'ms_kmeans_assign': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
+  'ms_kmeans_update': (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p]),
 }
 
 

@@ -275,6 +275,12 @@ class Gaussians3D(TensorClass):
     from .scene_io import save_ply
     save_ply(self, path, chunk_rows=chunk_rows)
 
+  def compressed(self, sh_codes: int = 4096, iterations: int = 10, weights: Optional[torch.Tensor] = None,
+                 seed: Optional[int] = None):
+    """The scene with its higher SH bands vector-quantised (``scene_codec.compress_scene``)."""
+    from .scene_codec import compress_scene
+    return compress_scene(self, sh_codes=sh_codes, iterations=iterations, weights=weights, seed=seed)
+
 
 def similarity_from_matrix(m) -> Tuple[float, torch.Tensor, torch.Tensor]:
   """``(s, R, t)`` of ``m = [[s R, t], [0, 1]]``, float64 on the CPU, or ``ValueError``: ``m`` must be (4, 4) with last

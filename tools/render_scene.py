@@ -10,7 +10,7 @@ gaussians and tile overlaps; ms per frame is the median over the views after one
 --out the images are written as view_000.npy ... (H, W, 3) float32.
 
     python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d] [--transform "x 90 0.5"]
-                                           [--coverage]
+                                           [--coverage] [--sh-codes K]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 --transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
@@ -18,6 +18,10 @@ similarity matrix) moves the scene after loading, SH bands included (Gaussians3D
 orbit the moved scene.
 --coverage runs camera_coverage over the orbit before rendering and adds to the JSON line the time of the call and how
 many gaussians are seen by no view, by some but not all (1..K-1), and by all K views (the three counts sum to N).
+--sh-codes K vector-quantises the higher SH bands with a K-code k-means codebook (scene_codec.compress_scene, 10 Lloyd
+iterations, seed 0), renders the decoded scene beside the original from every view and adds to the JSON line the two
+sizes in bytes, the time of the compression and the PSNR between the two renders (peak 1; per view and over all views).
+With --out the quantised images are written as quantised_000.npy ....
 """
 import argparse
 import json
@@ -99,6 +103,33 @@ def coverage_report(gaussians, cameras, config):
   return report
 
 
+def quantised_report(gaussians, cameras, config, sh_codes, sh_degree, images, out):
+  """compress_scene + decode, one render per camera beside ``images`` (the original's): sizes, seconds, PSNR"""
+  from taichi_splatting_amd import compress_scene
+  torch.cuda.synchronize()
+  start = time.perf_counter()
+  scene = compress_scene(gaussians, sh_codes=sh_codes, iterations=10, seed=0)
+  torch.cuda.synchronize()
+  seconds = time.perf_counter() - start
+  decoded = scene.decode()
+  original_bytes = sum(t.numel() * t.element_size() for t in gaussians.shape_tensors() + (gaussians.feature,))
+  squared, per_view = [], []
+  with torch.no_grad():
+    for v, (camera, image) in enumerate(zip(cameras, images)):
+      other = render_gaussians(decoded, camera, config, use_sh=True, sh_degree=sh_degree).image
+      mse = float(((other.double() - image.double()) ** 2).mean())
+      squared.append(mse)
+      per_view.append(round(-10.0 * math.log10(mse), 3) if mse > 0 else None)
+      if out:
+        np.save(Path(out) / f'quantised_{v:03d}.npy', other.cpu().numpy())
+  mean = statistics.fmean(squared)
+  report = dict(sh_codes=sh_codes, compress_s=round(seconds, 4), original_bytes=original_bytes, quantised_bytes=scene.nbytes,
+                psnr_db=round(-10.0 * math.log10(mean), 3) if mean > 0 else None, psnr_db_per_view=per_view)
+  print(f"quantised: {sh_codes} codes in {seconds:.2f} s; {original_bytes} -> {scene.nbytes} bytes "
+        f"({original_bytes / scene.nbytes:.2f} x); PSNR between the two renders {report['psnr_db']} dB", file=sys.stderr, flush=True)
+  return report
+
+
 def main():
   p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
   p.add_argument('scene')
@@ -112,6 +143,8 @@ def main():
                       "(row-major 4x4 similarity matrix); SH bands are rotated with it")
   p.add_argument('--coverage', action='store_true',
                  help="before rendering, run camera_coverage over the orbit: time, and gaussians seen by 0, 1..K-1, all K views")
+  p.add_argument('--sh-codes', type=int, default=None, metavar='K',
+                 help="also render the scene with its higher SH bands quantised to a K-code codebook: sizes and PSNR")
   args = p.parse_args()
   try:
     transform = parse_transform(args.transform) if args.transform is not None else None
@@ -164,12 +197,19 @@ def main():
     out.mkdir(parents=True, exist_ok=True)
     for v, image in enumerate(images):
       np.save(out / f'view_{v:03d}.npy', image.cpu().numpy())
+  quantised = None
+  if args.sh_codes is not None:
+    try:
+      quantised = quantised_report(gaussians, cameras, config, args.sh_codes, args.sh_degree, images, args.out)
+    except ValueError as e:
+      sys.exit(f"render_scene: --sh-codes: {e}")
   print(json.dumps(dict(
     scene=str(args.scene), n=n, sh_degree=degree, sh_active_degree=args.sh_degree, transform=args.transform, image_size=list(args.size), views=args.views, orbit_radius=round(radius, 6),
     load_s=round(load_s, 4), read_s=round(timings['read_s'], 4), upload_ms=round(timings['upload_ms'], 3),
     unpack_ms=round(timings['unpack_ms'], 3), visible=visible, overlaps=overlaps,
     frame_ms=round(statistics.median(frame_ms), 4), frame_ms_per_view=[round(ms, 4) for ms in frame_ms],
-    images=str(args.out) if args.out else None, **({'coverage': coverage} if coverage is not None else {}))), flush=True)
+    images=str(args.out) if args.out else None, **({'coverage': coverage} if coverage is not None else {}),
+    **({'quantised': quantised} if quantised is not None else {}))), flush=True)
 
 
 if __name__ == '__main__':
