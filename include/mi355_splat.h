@@ -220,6 +220,23 @@ int ms_find_ranges(const void* sorted_keys, int64_t k, int key_bytes, int tile_s
 int ms_tile_depth_sort(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_keys,
                        int32_t* overlap_to_point, uint64_t* scratch, void* stream);
 
+/* The frame executor's direct-order mapper on its own, from the scanned overlap counts to the lists: the launch
+ * sequence ms_frame_map_raster runs when ms_frame_desc.mapper is MS_MAPPER_DIRECT, with no host read in it.  The
+ * overlaps are emitted in storage order as two streams — tile ids of 2 bytes (4 when the image has more than 65 536
+ * tiles) and payload words key32(depth) << 32 | point index (key32 as in ms_tile_emit_keys64) — sorted by tile id with
+ * the stable radix passes of ms_radix_sort_pairs, ranged, and every tile's run of payload words is sorted as it is.
+ * Same lists as ms_tile_emit_keys64 -> ms_radix_sort_pairs -> ms_find_ranges -> ms_tile_depth_sort.
+ * points7 (v, 7) float; cum (v + 1) from ms_exclusive_scan_i32 over the counts of ms_tile_count (a gaussian whose
+ * count is zero emits nothing); image_w / image_h padded to the tile size.  k_capacity: entries of
+ * out_overlap_to_point.  out_tile_ranges (tiles, 2), written whole.  out_counters: 8 int32 on the device —
+ * [0] = K = cum[v], [1] = K when K <= k_capacity, else 0, [2] = 1 on that overflow (nothing is emitted, every range is
+ * [0, 0)), the rest internal.  Scratch query: scratch == NULL -> *scratch_bytes. */
+int ms_map_tiles_direct(const float* points7, const void* depth, int depth_dtype, const int32_t* cum, int64_t v,
+                        int image_w, int image_h, int tile_size, float alpha_threshold, int tile_row_begin,
+                        int tile_row_end, int depth16, double ndc_near, double ndc_far, int64_t k_capacity,
+                        int32_t* out_overlap_to_point, int32_t* out_tile_ranges, int32_t* out_counters,
+                        void* scratch, size_t* scratch_bytes, void* stream);
+
 /* ---- rasterizer ------------------------------------------------------------------------------
  * _forward_kernel (rasterizer/forward.py:23-135).  points7 (V,7), features (V,F), tile_ranges
  * (T,2) int32 indexed by tile id = tx + ty * ceil(W/tile), overlap_to_point (K) int32.
@@ -365,8 +382,9 @@ int ms_raster_bwd_moments_rows(const float* rows, const int32_t* tile_ranges, co
  *     backward runs and g->moments (n, MS_MOMENT_ROW) must be zero on entry and is zero again on return;
  *     otherwise g->grad_points7 / grad_colours are zero-initialised accumulators of ms_raster_bwd. */
 /* Two launch sequences build the same overlap_to_point / tile_ranges (same order, ties included):
- *   MS_MAPPER_DIRECT   overlaps emitted in storage order with keys tile << 32 | depth key, stable sort on the tile bits,
- *                      per-tile depth sort (ms_tile_depth_sort).  92 bytes moved per overlap, nothing per gaussian
+ *   MS_MAPPER_DIRECT   overlaps emitted in storage order as a 2-byte tile id (4 beyond 65 536 tiles) and an 8-byte
+ *                      payload depth key << 32 | point, stable sort on the tile bits, per-tile depth sort of the
+ *                      payload runs (ms_map_tiles_direct).  68 bytes moved per overlap, nothing per gaussian
  *                      beyond the count / emit passes: the faster one up to about 3.5 overlaps per gaussian.
  *   MS_MAPPER_PRESORT  gaussians sorted by depth first (4 passes over n pairs), overlaps counted and emitted in that
  *                      order, stable sort of (tile id, point) on the tile bits: 52 bytes per overlap.

@@ -145,12 +145,49 @@ static void frame_layout(const ms_frame_desc* d, ms_frame_layout* L) {
   L->split_scratch = keep_k.take(frame_uses_split(d) ? split_scratch_bytes(d->k_capacity, d->raster.tile_size, frame_split_params(d)) : 0);
   L->keep_k_bytes = keep_k.off;
 
-  // 8 byte keys (tile << 32 | depth key) of the direct-order mapper; the pre-sort path (MS_MAPPER=presort) uses half
+  // direct-order mapper: two buffers of 8 byte payload words (depth key << 32 | point) in `keys` / `keys_sorted`, two
+  // of tile ids (2 or 4 bytes) in `values` and behind the histogram of tmp_k (DirectMapBufs).  The pre-sort path
+  // (MS_MAPPER=presort) has 4 byte keys and values in the same regions and all of tmp_k as its sort scratch
   L->keys = scratch_k.take(k * 8);
   L->values = scratch_k.take(k * 4);
   L->keys_sorted = scratch_k.take(k * 8);
-  L->tmp_k = scratch_k.take(sort_tmp_size(d->k_capacity, 8));
+  L->tmp_k = scratch_k.take(sort_tmp_size(d->k_capacity, 4));
   L->scratch_k_bytes = scratch_k.off;
+}
+
+// ---- the direct-order mapper from the scanned overlap counts to (overlap_to_point, tile_ranges) ------------------
+struct DirectMapBufs {
+  void *ids_out, *ids_alt;                  // capacity tile ids each (tile_id_bytes)
+  uint64_t *payload_out, *payload_alt;      // capacity payload words each
+  char* hist_tmp;                           // sort_hist_size(capacity)
+};
+struct DirectMapGrid {
+  int w_pad, h_pad, tile_size, tiles_wide, num_tiles, tile_bits, row_begin, row_end;
+  float alpha_threshold;
+};
+
+// emit (tile id, payload) in storage order -> stable sort on the id bits -> ranges -> every run sorted by its payload
+// words.  counters: [1] = live K (0 on overflow: every kernel then finds nothing to do), [3..5] the per-tile sort's
+// words (frame_prepare_kernel); ranges zeroed on the stream already
+static int direct_map_enqueue(const float* points_f32, const void* depth, int dtype, const int32_t* cum, int64_t n,
+                              const DirectMapGrid& g, int depth16, double ndc_near, double ndc_far, int64_t capacity,
+                              int32_t* counters, const DirectMapBufs& b, int32_t* ranges, int32_t* o2p,
+                              int32_t* longest_run_host, hipStream_t s) {
+  const int id_bytes = tile_id_bytes(g.num_tiles);
+  const bool in_out = tile_sort_starts_in_out(g.tile_bits);
+  tile_emit_ids_launch(points_f32, depth, dtype, cum, n, g.w_pad, g.h_pad, g.tile_size, g.alpha_threshold, g.row_begin,
+                       g.row_end, depth16, ndc_near, ndc_far, counters + 1, id_bytes, in_out ? b.ids_out : b.ids_alt,
+                       in_out ? b.payload_out : b.payload_alt, s);
+  sort_ids_payload_dev_launch(id_bytes, b.ids_out, b.payload_out, b.ids_alt, b.payload_alt, capacity, counters + 1,
+                              g.tile_bits, b.hist_tmp, s);
+  const int rc = find_ranges_ids_dev_launch(id_bytes, b.ids_out, capacity, counters + 1, g.num_tiles, ranges, s);
+  if (rc != 0) return rc;
+  // only the strip's tile rows have runs (a rank of 8 would launch 57 344 workgroups that find an empty range)
+  const int64_t first_tile = (int64_t)g.row_begin * g.tiles_wide;
+  const int64_t strip_tiles = (int64_t)(g.row_end > g.row_begin ? g.row_end - g.row_begin : 0) * g.tiles_wide;
+  tile_payload_sort_launch(ranges + 2 * first_tile, strip_tiles, b.payload_out, o2p, b.payload_alt, s, counters + 3,
+                           longest_run_host);
+  return 0;
 }
 
 // What ms_frame_map_raster needs before its first real kernel, in ONE launch (a launch boundary costs ~5 us on this
@@ -391,21 +428,16 @@ extern "C" int ms_frame_map_raster(const ms_frame_desc* desc, const ms_frame_inp
       sort_pairs_u32_dev_launch(keys, values, keys_sorted, o2p, d.k_capacity, counters + 1, g.tile_bits, sk + L.tmp_k, s);
       MS_TRY(find_ranges_dev_launch(keys_sorted, d.k_capacity, counters + 1, g.num_tiles, ranges, s, true));
     } else {
-      uint64_t* keys = (uint64_t*)(sk + L.keys);
-      uint64_t* keys_sorted = (uint64_t*)(sk + L.keys_sorted);
       const void* depth = d.projected_input ? in->depth : (const void*)(kn + L.depth);
       const float* points_f32 = d.dtype == MS_F64 ? (const float*)(sn + L.points7_f32)
                                                   : (const float*)(d.projected_input ? in->points7 : (const void*)(kn + L.points7));
-      tile_emit_direct_launch(points_f32, depth, d.dtype, (const int32_t*)(sn + L.cum), d.n, g.w_pad, g.h_pad,
-                              d.raster.tile_size, (float)d.raster.alpha_threshold, g.row_begin, g.row_end, d.depth16,
-                              d.near_plane > 0.0 ? d.near_plane : 0.0, d.far_plane, counters + 1, keys, values, s);
-      sort_pairs_u64_dev_launch(keys, values, keys_sorted, o2p, d.k_capacity, counters + 1, 32, 32 + g.tile_bits,
-                                sk + L.tmp_k, s);
-      MS_TRY(find_ranges_u64_dev_launch(keys_sorted, d.k_capacity, counters + 1, g.num_tiles, ranges, s));
-      // only the strip's tile rows have runs (a rank of 8 would launch 57 344 workgroups that find an empty range)
-      const int64_t first_tile = (int64_t)g.row_begin * g.tiles_wide;
-      const int64_t strip_tiles = (int64_t)(g.row_end > g.row_begin ? g.row_end - g.row_begin : 0) * g.tiles_wide;
-      tile_depth_sort_launch(ranges + 2 * first_tile, strip_tiles, keys_sorted, o2p, keys, s, counters + 3, in->longest_run_host);
+      const DirectMapBufs bufs{values, sk + L.tmp_k + sort_hist_size(d.k_capacity), (uint64_t*)(sk + L.keys_sorted),
+                               (uint64_t*)(sk + L.keys), sk + L.tmp_k};
+      const DirectMapGrid grid{g.w_pad, g.h_pad, d.raster.tile_size, g.tiles_wide, g.num_tiles, g.tile_bits, g.row_begin,
+                               g.row_end, (float)d.raster.alpha_threshold};
+      MS_TRY(direct_map_enqueue(points_f32, depth, d.dtype, (const int32_t*)(sn + L.cum), d.n, grid, d.depth16,
+                                d.near_plane > 0.0 ? d.near_plane : 0.0, d.far_plane, d.k_capacity, counters, bufs, ranges,
+                                o2p, in->longest_run_host, s));
     }
   }
   MS_CHECK_LAUNCH();
@@ -421,6 +453,58 @@ extern "C" int ms_frame_map_raster(const ms_frame_desc* desc, const ms_frame_inp
   return raster_fwd_launch(points7, colours, frame_uses_rows(desc) ? (const float*)(kn + L.splat_rows) : nullptr, ranges, o2p,
                            d.image_w, d.image_h, d.f, &d.raster, out_image, out_alpha, out_visibility, g.row_begin, g.row_end,
                            d.dtype, stream, cut ? &split : nullptr, in->longest_run_host);
+}
+
+extern "C" int ms_map_tiles_direct(const float* points7, const void* depth, int depth_dtype, const int32_t* cum, int64_t v,
+                                   int image_w, int image_h, int tile_size, float alpha_threshold, int tile_row_begin,
+                                   int tile_row_end, int depth16, double ndc_near, double ndc_far, int64_t k_capacity,
+                                   int32_t* out_overlap_to_point, int32_t* out_tile_ranges, int32_t* out_counters,
+                                   void* scratch, size_t* scratch_bytes, void* stream) {
+  MS_CHECK_ARG(v >= 0 && v < (1ll << 31) && k_capacity >= 0 && k_capacity < (1ll << 31), "sizes are int32 indexes (< 2^31)");
+  MS_CHECK_ARG(depth_dtype == MS_F32 || depth_dtype == MS_F64, "depth_dtype must be MS_F32 or MS_F64");
+  MS_CHECK_ARG(tile_size > 0 && image_w > 0 && image_h > 0, "bad image/tile size");
+  MS_CHECK_ARG(image_w % tile_size == 0 && image_h % tile_size == 0, "image size must be padded to the tile size");
+  MS_CHECK_ARG(scratch_bytes != nullptr, "scratch_bytes is null");
+  DirectMapGrid g;
+  g.w_pad = image_w; g.h_pad = image_h; g.tile_size = tile_size;
+  g.tiles_wide = image_w / tile_size;
+  const int tiles_high = image_h / tile_size;
+  MS_CHECK_ARG((int64_t)g.tiles_wide * tiles_high < (1ll << 31), "too many tiles");
+  g.num_tiles = g.tiles_wide * tiles_high;
+  g.tile_bits = 1;
+  while ((1ll << g.tile_bits) < (long long)g.num_tiles) ++g.tile_bits;
+  g.row_begin = tile_row_begin < 0 ? 0 : tile_row_begin;
+  g.row_end = tile_row_end > tiles_high ? tiles_high : tile_row_end;
+  g.alpha_threshold = alpha_threshold;
+  MS_CHECK_ARG(!depth16 || g.num_tiles <= 65536, "use_depth16 keys hold a 16 bit tile id: too many tiles");
+
+  Carve c;
+  const size_t k = (size_t)k_capacity;
+  const size_t payload_out = c.take(k * 8), payload_alt = c.take(k * 8), ids_out = c.take(k * 4), ids_alt = c.take(k * 4);
+  const size_t hist = c.take(sort_hist_size(k_capacity));
+  if (scratch == nullptr) { *scratch_bytes = c.off; return 0; }
+  if (*scratch_bytes < c.off) { set_error("ms_map_tiles_direct: scratch too small (%zu < %zu)", *scratch_bytes, c.off); return MS_ERR_TMP_TOO_SMALL; }
+  MS_CHECK_ARG(out_tile_ranges && out_counters, "null pointer");
+  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "scratch must be 16-byte aligned");
+
+  hipStream_t s = (hipStream_t)stream;
+  MS_CHECK_HIP(hipMemsetAsync(out_counters, 0, 8 * sizeof(int32_t), s));
+  if (v > 0) {
+    MS_CHECK_ARG(cum != nullptr, "cum is null");
+    MS_CHECK_HIP(hipMemcpyAsync(out_counters, cum + v, sizeof(int32_t), hipMemcpyDeviceToDevice, s));      // K
+  }
+  const int64_t words = (int64_t)g.num_tiles * 2;
+  frame_prepare_kernel<float><<<dim3((unsigned)div_up(words, 256)), dim3(256), 0, s>>>(out_counters, (int32_t)k_capacity, nullptr,
+                                                                                      nullptr, out_tile_ranges, words);
+  if (v > 0 && k_capacity > 0) {
+    MS_CHECK_ARG(points7 && depth && out_overlap_to_point, "null pointer");
+    char* sc = (char*)scratch;
+    const DirectMapBufs bufs{sc + ids_out, sc + ids_alt, (uint64_t*)(sc + payload_out), (uint64_t*)(sc + payload_alt), sc + hist};
+    MS_TRY(direct_map_enqueue(points7, depth, depth_dtype, cum, v, g, depth16, ndc_near > 0.0 ? ndc_near : 0.0, ndc_far,
+                              k_capacity, out_counters, bufs, out_tile_ranges, out_overlap_to_point, nullptr, s));
+  }
+  MS_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int ms_frame_backward(const ms_frame_desc* desc, const ms_frame_inputs* in, void* keep_n, void* keep_k,

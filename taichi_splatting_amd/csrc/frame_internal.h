@@ -59,11 +59,19 @@ void sort_pairs_u32_dev_launch(const uint32_t* keys_in, const int32_t* vals_in, 
 int find_ranges_dev_launch(const uint32_t* sorted_keys, int64_t capacity, const int32_t* k_dev, int64_t num_tiles,
                            int32_t* out_ranges, hipStream_t s, bool zeroed = false);
 
-// the same on u64 keys, bits [begin_bit, end_bit) (direct-order mapper: tile id in bits 32.., depth key below)
-void sort_pairs_u64_dev_launch(const uint64_t* keys_in, const int32_t* vals_in, uint64_t* keys_out, int32_t* vals_out,
-                               int64_t capacity, const int32_t* n_dev, int begin_bit, int end_bit, char* tmp, hipStream_t s);
-// ranges of keys >> 32; the caller has zeroed out_ranges on the stream
-int find_ranges_u64_dev_launch(const uint64_t* sorted_keys, int64_t capacity, const int32_t* k_dev, int64_t num_tiles,
+// direct-order mapper: the overlaps are a stream of narrow tile ids (2 bytes while the launch has at most 65 536 tiles,
+// 4 beyond) and a stream of u64 payload words depth key << 32 | point index
+inline int tile_id_bytes(int64_t num_tiles) { return num_tiles <= 65536 ? 2 : 4; }
+// which of the two buffer pairs the emit pass fills so that the sorted pairs end in (ids_out, payload_out): the sort
+// ping-pongs between out and alt and its LAST pass writes out, so an even pass count starts from out itself
+inline bool tile_sort_starts_in_out(int tile_bits) { return ((tile_bits + 7) / 8) % 2 == 0; }
+size_t sort_hist_size(int64_t n);        // bytes of hist_tmp below
+// stable radix sort of (id, payload) pairs on id bits [0, tile_bits), same passes and digit split as the sorts above;
+// reads the pairs from out (tile_sort_starts_in_out) or alt, leaves them sorted in out and alt as scratch
+void sort_ids_payload_dev_launch(int id_bytes, void* ids_out, uint64_t* payload_out, void* ids_alt, uint64_t* payload_alt,
+                                 int64_t capacity, const int32_t* n_dev, int tile_bits, char* hist_tmp, hipStream_t s);
+// ranges of the sorted ids; the caller has zeroed out_ranges on the stream
+int find_ranges_ids_dev_launch(int id_bytes, const void* sorted_ids, int64_t capacity, const int32_t* k_dev, int64_t num_tiles,
                                int32_t* out_ranges, hipStream_t s);
 
 // ---- mapper.hip -------------------------------------------------------------------------------------------------
@@ -87,6 +95,12 @@ void tile_emit_direct_launch(const float* points7, const void* depth, int dtype,
                              double ndc_near, double ndc_far, const int32_t* k_limit_dev, uint64_t* out_keys,
                              int32_t* out_values, hipStream_t s);
 
+// the two-stream form of the emission (id_bytes: tile_id_bytes of the launch)
+void tile_emit_ids_launch(const float* points7, const void* depth, int dtype, const int32_t* cum, int64_t v, int image_w,
+                          int image_h, int tile_size, float alpha_threshold, int row_begin, int row_end, int depth16,
+                          double ndc_near, double ndc_far, const int32_t* k_limit_dev, int id_bytes, void* out_tiles,
+                          uint64_t* out_payload, hipStream_t s);
+
 // ---- tile_sort.hip ----------------------------------------------------------------------------------------------
 // Sorts every tile's run of `sorted_keys` (tile << 32 | depth key, already grouped by tile with the point indices in
 // `overlap_to_point` ascending inside each run) by (depth key, point index); only overlap_to_point is rewritten.
@@ -96,6 +110,10 @@ void tile_emit_direct_launch(const float* points7, const void* depth, int dtype,
 // entries if there is one.
 void tile_depth_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_keys, int32_t* overlap_to_point,
                             uint64_t* scratch, hipStream_t s, int32_t* run_stats = nullptr, int32_t* run_host = nullptr);
+
+// The same on runs of payload words depth key << 32 | point index (grouped by tile): overlap_to_point is output only.
+void tile_payload_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_payload, int32_t* overlap_to_point,
+                              uint64_t* scratch, hipStream_t s, int32_t* run_stats = nullptr, int32_t* run_host = nullptr);
 
 // ---- projection.hip ---------------------------------------------------------------------------------------------
 // ms_project_fwd; splat_rows (float32): also fills words 0..7 of each gaussian's splat row (common.h) and, when colours_in

@@ -230,6 +230,34 @@ tile_emit_direct_kernel(const float* __restrict__ points, const T* __restrict__ 
   });
 }
 
+// The same emission as two streams: tiles[o] = tile id (u16 while the launch has at most 65 536 tiles, u32 beyond) and
+// payload[o] = depth_sort_key(depth) << 32 | point index.  The stable sort on the tile bits then reads and moves 2 + 8
+// bytes per overlap instead of 8 + 4 and its histograms read the ids alone; the per-tile depth sort ranks the payload
+// words as they are (tile_sort.hip).
+template <typename T, typename IdT>
+__global__ void __launch_bounds__(256)
+tile_emit_ids_kernel(const float* __restrict__ points, const T* __restrict__ depth, const int32_t* __restrict__ cum,
+                     int64_t v, int image_w, int image_h, int tile_size, float alpha_threshold, int row_begin,
+                     int row_end, int depth16, double near_plane, double far_plane,
+                     const int32_t* __restrict__ k_limit, IdT* __restrict__ tiles, uint64_t* __restrict__ payload) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k_limit && *k_limit == 0) return;                // overflow of the caller's capacity: write nothing (uniform)
+  const int64_t first = i < v ? (int64_t)cum[i] : 0;
+  const bool valid = i < v && cum[i + 1] != first;     // not culled, and overlaps a tile of this strip
+  float g[7] = {0.f, 0.f, 1.f, 0.f, 1.f, 1.f, 0.f};
+  if (valid) load_point7(points, i, g);
+  const ObbQuery q = obb_grid_query(g, image_w, image_h, tile_size, alpha_threshold);
+  const int tiles_wide = image_w / tile_size;
+  const uint32_t depth_key = valid ? (uint32_t)depth_sort_key(depth[i], depth16, near_plane, far_plane) : 0u;
+  emit_span(q, valid, first, tile_size, row_begin, row_end, [&](int64_t o, int tx, int ty, int from) {
+    uint32_t dk = depth_key;
+    int32_t who = (int32_t)i;
+    if (from >= 0) { dk = (uint32_t)__builtin_amdgcn_readlane((int)depth_key, from); who = __builtin_amdgcn_readlane((int32_t)i, from); }
+    tiles[o] = (IdT)(tx + ty * tiles_wide);
+    payload[o] = ((uint64_t)dk << 32) | (uint32_t)who;
+  });
+}
+
 // 32 bit sort keys of the depth pre-sort: float bits (non-negative depths) or the 16 bit quantisation.
 // near_plane > 0 fuses ndc_depth (torch_lib/projection.py:120-123, renderer.py:67): evaluated in double
 // from the depth's own precision, then rounded once to the float the key is made of.
@@ -284,6 +312,17 @@ void tile_emit_direct_launch(const float* points7, const void* depth, int dtype,
     tile_emit_direct_kernel<float><<<grid, block, 0, s>>>(points7, (const float*)depth, cum, v, image_w, image_h, tile_size,
                                                           alpha_threshold, row_begin, row_end, depth16, ndc_near, ndc_far,
                                                           k_limit_dev, out_keys, out_values);
+}
+
+void tile_emit_ids_launch(const float* points7, const void* depth, int dtype, const int32_t* cum, int64_t v, int image_w,
+                          int image_h, int tile_size, float alpha_threshold, int row_begin, int row_end, int depth16,
+                          double ndc_near, double ndc_far, const int32_t* k_limit_dev, int id_bytes, void* out_tiles,
+                          uint64_t* out_payload, hipStream_t s) {
+  const dim3 grid((unsigned)div_up(v, 256)), block(256);
+#define MS_EMIT_IDS(T, IdT) tile_emit_ids_kernel<T, IdT><<<grid, block, 0, s>>>(points7, (const T*)depth, cum, v, image_w, image_h, tile_size, alpha_threshold, row_begin, row_end, depth16, ndc_near, ndc_far, k_limit_dev, (IdT*)out_tiles, out_payload)
+  if (dtype == MS_F64) { if (id_bytes == 2) MS_EMIT_IDS(double, uint16_t); else MS_EMIT_IDS(double, uint32_t); }
+  else { if (id_bytes == 2) MS_EMIT_IDS(float, uint16_t); else MS_EMIT_IDS(float, uint32_t); }
+#undef MS_EMIT_IDS
 }
 
 }  // namespace ms

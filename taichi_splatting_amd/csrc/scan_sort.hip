@@ -1,7 +1,8 @@
 // scan_sort.hip — integer primitives of the tile mapper, hand-written for wave64:
 //   * exclusive prefix sum of int32 (replaces cub::DeviceScan::ExclusiveSum, full_cumsum.cu:17-47)
 //   * stable LSD radix sort of (key, int32 value) pairs, 8-bit digits, u32/u64 keys
-//     (replaces cub::DeviceRadixSort::SortPairs, radix_sort_pairs.cu:8-70)
+//     (replaces cub::DeviceRadixSort::SortPairs, radix_sort_pairs.cu:8-70); the frame executor's direct-order mapper
+//     runs the same passes on u16/u32 tile ids with a u64 (depth key, point) payload as the value
 //   * segmented pair sort (cub::DeviceSegmentedSort::SortPairs, segmented_sort_pairs.cu:9-73;
 //     not on the render path — kept for API parity)
 //
@@ -202,13 +203,26 @@ __device__ __forceinline__ unsigned key_digit(KeyT k, int shift, unsigned mask) 
 // depth pre-sort makes its keys on the fly — float bits of the (ndc) depth or the 16-bit quantisation, exactly
 // depth_sort_key() of mapper.hip's depth_keys_kernel — and the value is the item's index: no key / value arrays are
 // written or read before the first scatter (ms_depth_argsort).
+// WidePairs: PlainPairs with an 8-byte value — narrow tile ids that carry `depth key << 32 | point` (direct-order mapper).
 template <typename KeyT> struct PlainPairs {
+  using value_type = int32_t;
+  static constexpr bool dense_keys = true;       // key(i) is keys[i]: a histogram may read them in any grouping
   const KeyT* keys;
   const int32_t* vals;
   __device__ __forceinline__ KeyT key(int64_t i) const { return keys[i]; }
   __device__ __forceinline__ int32_t val(int64_t i) const { return vals[i]; }
 };
+template <typename KeyT> struct WidePairs {
+  using value_type = uint64_t;
+  static constexpr bool dense_keys = true;
+  const KeyT* keys;
+  const uint64_t* vals;
+  __device__ __forceinline__ KeyT key(int64_t i) const { return keys[i]; }
+  __device__ __forceinline__ uint64_t val(int64_t i) const { return vals[i]; }
+};
 template <typename T> struct DepthPairs {
+  using value_type = int32_t;
+  static constexpr bool dense_keys = false;
   const T* depth;
   int depth16;
   double near_plane, far_plane;
@@ -240,7 +254,26 @@ __device__ __forceinline__ void upsweep_block(const Source src, int64_t n, int s
   unsigned* mine = cnt[wave][lane & (RS_COPIES - 1)];
   const int64_t base = (int64_t)blockIdx.x * RS_TILE + (int64_t)wave * RS_WAVE_ITEMS + lane;
   unsigned v_or = 0u, v_and = ~0u;
-  if ((int64_t)(blockIdx.x + 1) * RS_TILE <= n) {        // every item of the block exists: no bounds checks
+  bool counted = false;
+  if constexpr (sizeof(KeyT) == 2 && Source::dense_keys && !VARY) {
+    // 2-byte keys: a histogram does not care which thread counts which key, so a thread of a complete block takes
+    // RS_ROUNDS consecutive ones from two 128-bit loads instead of RS_ROUNDS 2-byte loads (block bases are multiples of
+    // 8 KB; the array itself must be 16-byte aligned, which every caller's carve gives)
+    if ((int64_t)(blockIdx.x + 1) * RS_TILE <= n && (reinterpret_cast<uintptr_t>(src.keys) & 15) == 0) {
+      static_assert(RS_ROUNDS == 16, "two uint4 per thread");
+      const uint4* p = reinterpret_cast<const uint4*>(src.keys + (int64_t)blockIdx.x * RS_TILE + (int64_t)threadIdx.x * RS_ROUNDS);
+      const uint4 a = p[0], b = p[1];
+      const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        atomicAdd(&mine[key_digit((KeyT)(w[j] & 0xffffu), shift, mask)], 1u);
+        atomicAdd(&mine[key_digit((KeyT)(w[j] >> 16), shift, mask)], 1u);
+      }
+      counted = true;
+    }
+  }
+  if (counted) {
+  } else if ((int64_t)(blockIdx.x + 1) * RS_TILE <= n) {        // every item of the block exists: no bounds checks
     KeyT k[RS_ROUNDS];
 #pragma unroll
     for (int j = 0; j < RS_ROUNDS; ++j) k[j] = src.key(base + j * 64);
@@ -321,23 +354,25 @@ radix_row_scan_kernel(int32_t* __restrict__ hist, int64_t num_blocks, int32_t* _
   row_scan_body(hist, num_blocks, digit_totals);
 }
 
-template <typename KeyT> struct DownsweepShared {
+template <typename KeyT, typename ValT> struct DownsweepShared {
   unsigned cnt[RS_WAVES][RS_RADIX];
   int scan[4];
   // global start of this block's run of digit d MINUS the block-local start of the digit: an item at local position idx
   // goes to digit_shift[d] + idx (unsigned wrap-around is fine).  One array instead of two: with 8-byte keys the block's
-  // LDS is 54 288 bytes instead of 55 312, i.e. three workgroups per CU instead of two (tools/kernel_resources.py)
+  // LDS is 54 288 bytes instead of 55 312, i.e. three workgroups per CU instead of two (tools/kernel_resources.py);
+  // 2-byte keys with 8-byte values: 46 096 bytes, three as well
   unsigned digit_shift[RS_RADIX];
+  ValT vals[RS_TILE];
   KeyT keys[RS_TILE];
-  int32_t vals[RS_TILE];
 };
 
 // FULL: every one of the block's RS_TILE items exists (all blocks but the last): no bounds checks at all.  With
 // them each of the 32 loads of a thread sat in its own EXEC-masked block behind a 64-bit compare, and the ranking and
 // the scatter carried a validity flag per item.
 template <typename KeyT, bool FULL, typename Source>
-__device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT>& sh, const Source src, KeyT* __restrict__ keys_out,
-                                                int32_t* __restrict__ vals_out, int64_t n, int shift, unsigned mask,
+__device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT, typename Source::value_type>& sh, const Source src,
+                                                KeyT* __restrict__ keys_out,
+                                                typename Source::value_type* __restrict__ vals_out, int64_t n, int shift, unsigned mask,
                                                 const int32_t* __restrict__ hist_scanned,
                                                 const int32_t* __restrict__ digit_totals, int64_t num_blocks) {
   for (int i = threadIdx.x; i < RS_WAVES * RS_RADIX; i += RS_THREADS) (&sh.cnt[0][0])[i] = 0;
@@ -347,8 +382,9 @@ __device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT>& sh, const
   const int64_t base = (int64_t)blockIdx.x * RS_TILE + (int64_t)wave * RS_WAVE_ITEMS + lane;
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
 
+  using ValT = typename Source::value_type;
   KeyT k[RS_ROUNDS];
-  int32_t v[RS_ROUNDS];
+  ValT v[RS_ROUNDS];
   unsigned rank[RS_ROUNDS];   // rank of the item among equal digits of this wave
 
 #pragma unroll
@@ -356,7 +392,7 @@ __device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT>& sh, const
     const int64_t i = base + j * 64;
     const bool valid = FULL || i < n;
     k[j] = valid ? src.key(i) : (KeyT)0;
-    v[j] = valid ? src.val(i) : 0;
+    v[j] = valid ? src.val(i) : (ValT)0;
   }
 
 #pragma unroll
@@ -446,11 +482,11 @@ __device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT>& sh, const
 template <typename KeyT, typename Source>
 __global__ void __launch_bounds__(RS_THREADS)
 radix_downsweep_kernel(const Source src,
-                       KeyT* __restrict__ keys_out, int32_t* __restrict__ vals_out, int64_t n,
+                       KeyT* __restrict__ keys_out, typename Source::value_type* __restrict__ vals_out, int64_t n,
                        const int32_t* __restrict__ n_dev, int shift,
                        unsigned mask, const int32_t* __restrict__ hist_scanned,
                        const int32_t* __restrict__ digit_totals, int64_t num_blocks) {
-  __shared__ DownsweepShared<KeyT> sh;
+  __shared__ DownsweepShared<KeyT, typename Source::value_type> sh;
   if (n_dev) {
     n = *n_dev;
     if ((int64_t)blockIdx.x * RS_TILE >= n) return;
@@ -492,20 +528,21 @@ static SortTmp sort_tmp_layout(int64_t n, int key_bytes, bool adaptive = false) 
   return t;
 }
 
-// `first` = where pass 0 reads its pairs (PlainPairs of the caller's arrays, or DepthPairs); later passes read the
-// ping-pong buffers.
-template <typename KeyT, typename First>
-static int radix_sort_passes(const First first, KeyT* keys_out, int32_t* vals_out, int64_t n, int begin_bit, int end_bit,
-                             char* tmp, hipStream_t s, const int32_t* n_dev = nullptr) {
+// `first` = where pass 0 reads its pairs (PlainPairs / WidePairs of the caller's arrays, or DepthPairs); later passes read
+// the ping-pong buffers as `Plain` (PlainPairs<KeyT> or WidePairs<KeyT>: the value type).  The last pass writes to
+// out, the one before to alt, and so on: `first` may be the out arrays themselves when the pass count is even, the alt
+// arrays when it is odd (radix_pass_count) — the direct-order mapper sorts inside two buffers that way.
+static int radix_pass_count(int begin_bit, int end_bit) { return (end_bit - begin_bit + 7) / 8; }
+
+template <typename KeyT, typename Plain, typename First>
+static int radix_sort_passes_on(const First first, KeyT* keys_out, typename Plain::value_type* vals_out, KeyT* keys_alt,
+                                typename Plain::value_type* vals_alt, int32_t* hist, int32_t* digit_totals /* 256 ints */,
+                                int64_t n, int begin_bit, int end_bit, hipStream_t s, const int32_t* n_dev = nullptr) {
+  using ValT = typename Plain::value_type;
   const int64_t blocks = div_up(n, RS_TILE);
-  const SortTmp lay = sort_tmp_layout(n, sizeof(KeyT));
-  int32_t* hist = (int32_t*)(tmp + lay.hist_off);
-  int32_t* digit_totals = (int32_t*)(tmp + lay.scan_off);       // 256 ints
-  KeyT* keys_alt = (KeyT*)(tmp + lay.keys_off);
-  int32_t* vals_alt = (int32_t*)(tmp + lay.vals_off);
-  const int passes = (end_bit - begin_bit + 7) / 8;
+  const int passes = radix_pass_count(begin_bit, end_bit);
   const dim3 grid((unsigned)blocks), block(RS_THREADS);
-  PlainPairs<KeyT> src{nullptr, nullptr};
+  Plain src{nullptr, nullptr};
   // digits of equal width (14 tile bits = 7 + 7, not 8 + 6): fewer bins -> longer contiguous runs in the scatter
   const int total_bits = end_bit - begin_bit, base_bits = total_bits / passes, wide = total_bits % passes;
   int shift = begin_bit;
@@ -514,15 +551,25 @@ static int radix_sort_passes(const First first, KeyT* keys_out, int32_t* vals_ou
     const unsigned mask = (1u << bits) - 1u;
     const bool to_out = ((passes - 1 - p) % 2) == 0;
     KeyT* dst_k = to_out ? keys_out : keys_alt;
-    int32_t* dst_v = to_out ? vals_out : vals_alt;
+    ValT* dst_v = to_out ? vals_out : vals_alt;
     if (p == 0) radix_upsweep_kernel<KeyT, First><<<grid, block, 0, s>>>(first, n, n_dev, shift, mask, hist, blocks);
-    else radix_upsweep_kernel<KeyT, PlainPairs<KeyT>><<<grid, block, 0, s>>>(src, n, n_dev, shift, mask, hist, blocks);
+    else radix_upsweep_kernel<KeyT, Plain><<<grid, block, 0, s>>>(src, n, n_dev, shift, mask, hist, blocks);
     radix_row_scan_kernel<<<dim3(RS_RADIX), dim3(SCAN_THREADS), 0, s>>>(hist, blocks, digit_totals);
     if (p == 0) radix_downsweep_kernel<KeyT, First><<<grid, block, 0, s>>>(first, dst_k, dst_v, n, n_dev, shift, mask, hist, digit_totals, blocks);
-    else radix_downsweep_kernel<KeyT, PlainPairs<KeyT>><<<grid, block, 0, s>>>(src, dst_k, dst_v, n, n_dev, shift, mask, hist, digit_totals, blocks);
-    src = PlainPairs<KeyT>{dst_k, dst_v};
+    else radix_downsweep_kernel<KeyT, Plain><<<grid, block, 0, s>>>(src, dst_k, dst_v, n, n_dev, shift, mask, hist, digit_totals, blocks);
+    src = Plain{dst_k, dst_v};
   }
   return 0;
+}
+
+// (key, int32 value) pairs with the histogram and the alternate buffers carved from `tmp` (sort_tmp_layout)
+template <typename KeyT, typename First>
+static int radix_sort_passes(const First first, KeyT* keys_out, int32_t* vals_out, int64_t n, int begin_bit, int end_bit,
+                             char* tmp, hipStream_t s, const int32_t* n_dev = nullptr) {
+  const SortTmp lay = sort_tmp_layout(n, sizeof(KeyT));
+  return radix_sort_passes_on<KeyT, PlainPairs<KeyT>>(first, keys_out, vals_out, (KeyT*)(tmp + lay.keys_off),
+                                                      (int32_t*)(tmp + lay.vals_off), (int32_t*)(tmp + lay.hist_off),
+                                                      (int32_t*)(tmp + lay.scan_off), n, begin_bit, end_bit, s, n_dev);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -591,7 +638,7 @@ template <typename First>
 __global__ void __launch_bounds__(RS_THREADS)
 depth_downsweep_first_kernel(const First first, AdaptiveBufs b, int passes, int64_t n,
                              const int32_t* __restrict__ hist_scanned, const int32_t* __restrict__ digit_totals, int64_t num_blocks) {
-  __shared__ DownsweepShared<uint32_t> sh;
+  __shared__ DownsweepShared<uint32_t, int32_t> sh;
   bool active, last; int k;
   adaptive_route(b.vary[0], 0, passes, active, k, last);
   uint32_t* ko = last ? b.k_out : b.k_alt[0];
@@ -603,7 +650,7 @@ depth_downsweep_first_kernel(const First first, AdaptiveBufs b, int passes, int6
 __global__ void __launch_bounds__(RS_THREADS)
 depth_downsweep_kernel(AdaptiveBufs b, int p, int passes, int64_t n, const int32_t* __restrict__ hist_scanned,
                        const int32_t* __restrict__ digit_totals, int64_t num_blocks) {
-  __shared__ DownsweepShared<uint32_t> sh;
+  __shared__ DownsweepShared<uint32_t, int32_t> sh;
   bool active, last; int k;
   adaptive_route(b.vary[0], p, passes, active, k, last);
   if (!active) return;
@@ -715,27 +762,33 @@ find_ranges4_kernel(const uint32_t* __restrict__ keys, int64_t capacity, const i
   }
 }
 
-// frame executor, direct-order mapper: tile id = key >> 32 of u64 keys.  Two keys per thread from ONE 128-bit load (a wave
-// reads 2 KB contiguous); the key after them is the neighbour lane's first (lane 63 reads its own)
+// frame executor, direct-order mapper: the sorted narrow tile ids (u16 / u32) themselves.  PER = 16 bytes of ids per
+// thread from one 128-bit load + the id after them; the same output as find_ranges4_kernel
+template <typename IdT>
 __global__ void __launch_bounds__(256)
-find_ranges2_u64_kernel(const uint64_t* __restrict__ keys, int64_t capacity, const int32_t* __restrict__ k_dev,
-                        int64_t num_tiles, int32_t* __restrict__ ranges) {
-  const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 2;
+find_ranges_ids_kernel(const IdT* __restrict__ ids, int64_t capacity, const int32_t* __restrict__ k_dev,
+                       int64_t num_tiles, int32_t* __restrict__ ranges) {
+  constexpr int PER = 16 / (int)sizeof(IdT);
+  const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * PER;
   const int64_t k = k_dev ? (int64_t)*k_dev : capacity;
-  uint32_t t0 = 0xffffffffu, t1 = 0xffffffffu;               // 0xffffffff: no key
-  if (i0 + 1 < k) {
-    const uint4 a = *reinterpret_cast<const uint4*>(keys + i0);
-    t0 = a.y; t1 = a.w;
-  } else if (i0 < k) {
-    t0 = (uint32_t)(keys[i0] >> 32);
-  }
-  uint32_t t2 = (uint32_t)__shfl_down((int)t0, 1);
-  if ((threadIdx.x & 63) == 63) t2 = i0 + 2 < k ? (uint32_t)(keys[i0 + 2] >> 32) : 0xffffffffu;
   if (i0 >= k) return;
-  if (i0 == 0 && (int64_t)t0 < num_tiles) ranges[(int64_t)t0 * 2 + 0] = 0;
-  const uint32_t t[3] = {t0, t1, t2};
+  uint32_t t[PER + 1];
+  if (i0 + PER < k && (reinterpret_cast<uintptr_t>(ids) & 15) == 0) {
+    const uint4 v = *reinterpret_cast<const uint4*>(ids + i0);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < PER; ++j) {
+      if constexpr (sizeof(IdT) == 2) t[j] = (w[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+      else t[j] = w[j];
+    }
+    t[PER] = (uint32_t)ids[i0 + PER];
+  } else {
+#pragma unroll
+    for (int j = 0; j <= PER; ++j) t[j] = i0 + j < k ? (uint32_t)ids[i0 + j] : 0u;      // (past k: never looked at)
+  }
+  if (i0 == 0 && (int64_t)t[0] < num_tiles) ranges[(int64_t)t[0] * 2 + 0] = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
     const int64_t i = i0 + j;
     if (i >= k) break;
     const int64_t tile = t[j], next = (i + 1 < k) ? (int64_t)t[j + 1] : -1;
@@ -777,15 +830,31 @@ int find_ranges_dev_launch(const uint32_t* sorted_keys, int64_t capacity, const 
   return 0;
 }
 
-void sort_pairs_u64_dev_launch(const uint64_t* keys_in, const int32_t* vals_in, uint64_t* keys_out, int32_t* vals_out,
-                               int64_t capacity, const int32_t* n_dev, int begin_bit, int end_bit, char* tmp, hipStream_t s) {
-  radix_sort_passes<uint64_t>(PlainPairs<uint64_t>{keys_in, vals_in}, keys_out, vals_out, capacity, begin_bit, end_bit, tmp, s, n_dev);
+size_t sort_hist_size(int64_t n) { return sort_tmp_layout(n, 0).keys_off; }      // histogram + digit totals only
+
+template <typename IdT>
+static void sort_ids_payload(IdT* ids_out, uint64_t* payload_out, IdT* ids_alt, uint64_t* payload_alt, int64_t capacity,
+                             const int32_t* n_dev, int tile_bits, char* hist_tmp, hipStream_t s) {
+  const SortTmp lay = sort_tmp_layout(capacity, 0);
+  const bool even = radix_pass_count(0, tile_bits) % 2 == 0;
+  const WidePairs<IdT> first{even ? ids_out : ids_alt, even ? payload_out : payload_alt};
+  radix_sort_passes_on<IdT, WidePairs<IdT>>(first, ids_out, payload_out, ids_alt, payload_alt, (int32_t*)(hist_tmp + lay.hist_off),
+                                            (int32_t*)(hist_tmp + lay.scan_off), capacity, 0, tile_bits, s, n_dev);
 }
 
-int find_ranges_u64_dev_launch(const uint64_t* sorted_keys, int64_t capacity, const int32_t* k_dev, int64_t num_tiles,
+void sort_ids_payload_dev_launch(int id_bytes, void* ids_out, uint64_t* payload_out, void* ids_alt, uint64_t* payload_alt,
+                                 int64_t capacity, const int32_t* n_dev, int tile_bits, char* hist_tmp, hipStream_t s) {
+  if (id_bytes == 2) sort_ids_payload<uint16_t>((uint16_t*)ids_out, payload_out, (uint16_t*)ids_alt, payload_alt, capacity, n_dev, tile_bits, hist_tmp, s);
+  else sort_ids_payload<uint32_t>((uint32_t*)ids_out, payload_out, (uint32_t*)ids_alt, payload_alt, capacity, n_dev, tile_bits, hist_tmp, s);
+}
+
+int find_ranges_ids_dev_launch(int id_bytes, const void* sorted_ids, int64_t capacity, const int32_t* k_dev, int64_t num_tiles,
                                int32_t* out_ranges, hipStream_t s) {
-  if (capacity > 0)
-    find_ranges2_u64_kernel<<<dim3((unsigned)div_up(capacity, 512)), dim3(256), 0, s>>>(sorted_keys, capacity, k_dev, num_tiles, out_ranges);
+  if (capacity <= 0) return 0;
+  if (id_bytes == 2)
+    find_ranges_ids_kernel<uint16_t><<<dim3((unsigned)div_up(capacity, 256 * 8)), dim3(256), 0, s>>>((const uint16_t*)sorted_ids, capacity, k_dev, num_tiles, out_ranges);
+  else
+    find_ranges_ids_kernel<uint32_t><<<dim3((unsigned)div_up(capacity, 256 * 4)), dim3(256), 0, s>>>((const uint32_t*)sorted_ids, capacity, k_dev, num_tiles, out_ranges);
   return 0;
 }
 
