@@ -928,6 +928,37 @@ int ms_kmeans_update(const float* x, const int32_t* index, const float* weights 
                      int k, float* codebook, int32_t* out_counts, double* out_weight_sums /* may be NULL */, void* tmp,
                      size_t* tmp_bytes, void* stream);
 
+/* ---- colours of a vector-quantised scene from its stored form (no reference counterpart: an addition) ----
+ * colour_c(i) = clamp(0.5 + Y_0 dc[i, c] + sum_{d >= 1} Y_d(dir_i) codebook[index[i], c, d - 1], 0, 1) with
+ * dir_i = (positions[i] - cam_pos) / |.|: what ms_sh_fwd gives for the decoded rows cat(dc, codebook[index]), without
+ * the decoded (n, 3, D) tensor or its gradient.  float32, 3 channels, sh_degree 1..3 (the stored degree), 1 <= k <=
+ * 65 536, 0 <= n < 2^31 - 512.  dc (n, 3), index (n,) int32, codebook (k, 3, M) with M = (sh_degree + 1)^2 - 1,
+ * positions (n, 3), cam_pos (3,), out (n, 3).  An index outside 0..k-1 is clamped (wrong result, no stray access).
+ * Neither call reads on the host, allocates or synchronises: both capture into a graph.
+ *
+ * ms_sh_coded_fwd: one lane per gaussian in storage order; products summed for d = 0 .. D - 1, then + 0.5, then the
+ * clamp.  The code row is gathered as stored (4-byte aligned).  n == 0 launches nothing.
+ *
+ * ms_sh_coded_bwd: per channel g = g_out where 0 < out < 1 (out is the clamped colour the forward wrote), else 0.
+ *   g_dc[i, c] = g Y_0                                              dense, may be NULL
+ *   g_codebook[j, c, d - 1] = sum over index[i] == j of g_c(i) Y_d(dir_i)      every row written, may be NULL
+ * The codebook sum has no atomics and an order fixed by the plan, which the caller derives from index alone: the
+ * gaussians listed by code, stably (storage order inside a code); rank (n,) is the place of each gaussian in that list;
+ * the run of a code is cut into chunks of MS_SH_CODED_CHUNK entries, chunk_begin (num_chunks,) is the first entry of each
+ * chunk in list order (a chunk ends where the next begins), chunk_off (k + 1,) the first chunk of each code.  A
+ * storage-order pass writes (g, dir) of every gaussian into its place of the list, a workgroup sums the products
+ * (double)g (double)Y of one chunk, a wave adds the chunks of one code in list order and rounds to float32 once: two
+ * runs are bitwise equal.  Entries of the plan are clamped to their ranges.  With g_codebook == NULL only out and g_out
+ * are read.  tmp == NULL returns *tmp_bytes for (n, num_chunks, sh_degree): the chunk sums and 24 bytes per gaussian.
+ * MS_ERR_BAD_ARG names the argument. */
+#define MS_SH_CODED_CHUNK 512
+int ms_sh_coded_fwd(const float* dc, const int32_t* index, const float* codebook, const float* positions,
+                    const float* cam_pos, int64_t n, int k, int sh_degree, float* out, void* stream);
+int ms_sh_coded_bwd(const float* positions, const float* cam_pos, const float* out, const float* g_out,
+                    const int32_t* rank, const int32_t* chunk_begin, const int32_t* chunk_off, int64_t num_chunks, int64_t n,
+                    int k, int sh_degree, float* g_dc /* may be NULL */, float* g_codebook /* may be NULL */, void* tmp,
+                    size_t* tmp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,8 @@ from .misc.coverage import camera_coverage, pack_cameras, Coverage
 from .misc.relocate import relocate_gaussians3d, perturb_positions
 from .optim.relocate import relocate, RelocateResult
 from .misc.kmeans import kmeans, kmeans_assign, kmeans_update, KMeansResult
-from .scene_codec import compress_scene, load_compressed, CompressedScene
+from .scene_codec import compress_scene, load_compressed, CompressedScene, render_compressed
+from .spherical_harmonics import evaluate_sh_coded, make_coded_sh_plan, CodedSHPlan
 
 __version__ = '0.5.0'       # = MS_VERSION 500 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -40,6 +41,7 @@ __all__ = [
   'relocate', 'RelocateResult', 'relocate_gaussians3d', 'perturb_positions',
   'kmeans', 'kmeans_assign', 'kmeans_update', 'KMeansResult',
   'compress_scene', 'load_compressed', 'CompressedScene',
+  'render_compressed', 'evaluate_sh_coded', 'make_coded_sh_plan', 'CodedSHPlan',
 ]
 
 
@@ -56,7 +58,7 @@ def install_as_taichi_splatting():
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',
-              'examples.fit_image_gaussians'):
+              'examples.fit_image_gaussians', 'examples.finetune_compressed'):
     mod = importlib.import_module(f'{__name__}.{sub}')
     sys.modules.setdefault(f'taichi_splatting.{sub}', mod)
   # module names of the reference whose contents live elsewhere here: evaluate_sh_at (reference

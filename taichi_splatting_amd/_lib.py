@@ -36,6 +36,7 @@ RELOCATE_MAX_RATIO = 51         # MS_RELOCATE_MAX_RATIO: side of the binomial ta
 KMEANS_MAX_D, KMEANS_MAX_K = 64, 65536   # MS_KMEANS_MAX_D / MS_KMEANS_MAX_K
 KMEANS_CHUNK = 128              # MS_KMEANS_CHUNK: codes a workgroup of ms_kmeans_assign stages per pass
 KMEANS_UPDATE_CHUNK = 1024      # MS_KMEANS_UPDATE_CHUNK: sorted entries per workgroup of ms_kmeans_update
+SH_CODED_CHUNK = 512            # MS_SH_CODED_CHUNK: entries of the code order per workgroup of ms_sh_coded_bwd
 RELOCATE_COPY, RELOCATE_ZERO_TOUCHED, RELOCATE_INHERIT, RELOCATE_OPACITY, RELOCATE_SCALE = range(5)   # MS_RELOCATE_*
 
 _lib: Optional[ctypes.CDLL] = None
@@ -219,6 +220,8 @@ SIGNATURES = {
   'ms_perturb_positions': (c_int, [c_void_p] * 5 + [c_int64, c_float, c_double, c_double, c_void_p]),
   'ms_kmeans_assign': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
   'ms_kmeans_update': (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p]),
+  'ms_sh_coded_fwd': (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_void_p, c_void_p]),
+  'ms_sh_coded_bwd': (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_int, c_int] + [c_void_p] * 3 + [POINTER(c_size_t), c_void_p]),
 }
 
 

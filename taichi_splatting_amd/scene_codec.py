@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .data_types import Gaussians3D
+from .data_types import Gaussians3D, RasterConfig
 
 FORMAT_VERSION = 1
 _TENSORS = ('position', 'log_scaling', 'rotation', 'alpha_logit', 'dc', 'sh_codebook', 'sh_index')
@@ -69,6 +69,25 @@ class CompressedScene:
     arrays = {name: getattr(self, name).detach().cpu().numpy() for name in _TENSORS}
     arrays['sh_index'] = arrays['sh_index'].astype(np.uint16)
     np.savez(os.fspath(path), format_version=np.int32(FORMAT_VERSION), sh_degree=np.int32(self.sh_degree), **arrays)
+
+  def colours(self, camera_position: torch.Tensor) -> torch.Tensor:
+    """(N, 3) view-dependent colours seen from ``camera_position`` (3,), evaluated from ``dc``, ``sh_codebook`` and
+    ``sh_index`` as stored (``spherical_harmonics.evaluate_sh_coded``): nothing is decoded.  Differentiable in ``dc`` and
+    ``sh_codebook``.  The summation plan of the backward is kept on the scene and rebuilt when ``sh_index`` is another
+    tensor."""
+    from .spherical_harmonics import evaluate_sh_coded, make_coded_sh_plan
+    plan = getattr(self, '_coded_plan', None)
+    if plan is None or plan.index is not self.sh_index or plan.k != self.sh_codebook.shape[0]:
+      plan = make_coded_sh_plan(self.sh_index, self.sh_codebook.shape[0])
+      self._coded_plan = plan
+    return evaluate_sh_coded(self.dc, self.sh_index, self.sh_codebook, self.position.detach(), camera_position, plan=plan)
+
+  def view(self, camera_position: torch.Tensor) -> Gaussians3D:
+    """The scene as seen from ``camera_position``: a ``Gaussians3D`` whose ``feature`` is ``colours(camera_position)``
+    (plain (N, 3) colours, to be rendered with ``use_sh=False``) and whose other fields are the scene's own tensors."""
+    return Gaussians3D(position=self.position, log_scaling=self.log_scaling, rotation=self.rotation,
+                       alpha_logit=self.alpha_logit, feature=self.colours(camera_position),
+                       batch_size=(self.position.shape[0],))
 
 
 def load_compressed(path, device='cpu') -> CompressedScene:
@@ -134,4 +153,15 @@ def compress_scene(gaussians: Gaussians3D, sh_codes: int = 4096, iterations: int
                          sh_index=result.index, sh_degree=degree)
 
 
-__all__ = ['CompressedScene', 'compress_scene', 'load_compressed', 'FORMAT_VERSION']
+def render_compressed(scene: CompressedScene, camera_params, config: RasterConfig = RasterConfig(), **kwargs):
+  """``render_gaussians(scene.view(camera_params.camera_position), camera_params, config, use_sh=False, **kwargs)``: a
+  compressed scene rendered, and differentiated in ``dc``, ``sh_codebook`` and the geometry, without decoding it.  The
+  colours enter the renderer as plain features, so ``use_sh`` and ``sh_degree`` among the kwargs are a ValueError."""
+  from .renderer import render_gaussians
+  for name in ('use_sh', 'sh_degree'):
+    if name in kwargs:
+      raise ValueError(f"render_compressed: {name} is not a choice here (the stored SH degree is evaluated into plain colours)")
+  return render_gaussians(scene.view(camera_params.camera_position), camera_params, config, use_sh=False, **kwargs)
+
+
+__all__ = ['CompressedScene', 'compress_scene', 'load_compressed', 'render_compressed', 'FORMAT_VERSION']

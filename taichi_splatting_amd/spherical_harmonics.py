@@ -3,12 +3,16 @@
 Same interface as reference ``indexed_spherical_harmonics.py:166-177`` (``evaluate_sh_at``);
 forward/backward kernels in csrc/sh.hip (hand-derived backward instead of Taichi autodiff).
 
+``evaluate_sh_coded`` (no reference counterpart) evaluates the colours of a vector-quantised scene from its DC band,
+codebook and indices (csrc/sh_coded.hip), with a reproducible codebook gradient.
+
 ``sh_rotation_matrices`` / ``rotate_sh`` (no reference counterpart) rotate the bands of stored coefficients, the SH half
 of ``Gaussians3D.transformed`` (csrc/scene_transform.hip).
 """
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass, field
 import functools
 import math
 from typing import Optional
@@ -97,6 +101,145 @@ def evaluate_sh_at(sh_params: torch.Tensor,   # M, K, (degree + 1)^2  (usually K
   assert 0 <= degree <= 3, f"SH degree must be between 0 and 3, got {degree}"
   active = check_active_degree(active_degree, degree)
   return _SHFunction.apply(sh_params, positions, indexes, camera_pos, degree, unique_indexes, active)
+
+
+# ---- colours of a vector-quantised scene from its stored form (csrc/sh_coded.hip; no reference counterpart) ------------
+
+@dataclass
+class CodedSHPlan:
+  """The order in which ``ms_sh_coded_bwd`` sums the codebook gradient: a function of ``sh_index`` alone, so one plan
+  serves every frame and every step of a fine-tune.  ``index`` is the tensor the plan was built from."""
+  index: torch.Tensor         # (N,) int32
+  order: torch.Tensor         # (N,) int32: the gaussians listed by code, storage order inside a code (stable)
+  rank: torch.Tensor          # (N,) int32: the inverse of order, what the kernels read
+  chunk_code: torch.Tensor    # (num_chunks,) int32: the code of each chunk of SH_CODED_CHUNK entries
+  chunk_begin: torch.Tensor   # (num_chunks,) int32: its first entry of order
+  chunk_off: torch.Tensor     # (K + 1,) int32: the first chunk of each code; chunk_off[K] = num_chunks
+  num_chunks: int             # read on the host once, here
+  k: int
+  _scratch_bytes: dict = field(default_factory=dict, repr=False)      # degree -> bytes of ms_sh_coded_bwd's scratch
+
+  @property
+  def n(self) -> int:
+    return self.index.shape[0]
+
+
+def make_coded_sh_plan(sh_index: torch.Tensor, k: int) -> CodedSHPlan:
+  """Plain torch on the device of ``sh_index`` (the CPU too): stable sort, bincount, cumsum, repeat_interleave.  One host
+  read (the index range and the number of chunks).  ValueError on an index outside 0..k-1 or a dtype other than int32."""
+  if not isinstance(sh_index, torch.Tensor) or sh_index.ndim != 1:
+    raise ValueError(f"sh_index must be a 1D tensor, got {tuple(getattr(sh_index, 'shape', ()))}")
+  if sh_index.dtype != torch.int32:
+    raise ValueError(f"sh_index must be int32, got {sh_index.dtype}")
+  if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= 65536:
+    raise ValueError(f"k must be an integer in 1..65536, got {k!r}")
+  n, device, chunk = sh_index.shape[0], sh_index.device, _lib.SH_CODED_CHUNK
+  wide = sh_index.detach().long()
+  if n > 0:
+    lo, hi = (int(v) for v in torch.stack([wide.min(), wide.max()]).tolist())
+    if lo < 0 or hi >= k:
+      raise ValueError(f"sh_index must lie in 0..{k - 1}, got values in {lo}..{hi}")
+  order = torch.sort(wide, stable=True).indices
+  counts = torch.bincount(wide, minlength=k)
+  chunks_per = (counts + (chunk - 1)) // chunk
+  chunk_off = torch.zeros((k + 1,), dtype=torch.int64, device=device)
+  torch.cumsum(chunks_per, dim=0, out=chunk_off[1:])
+  start = torch.cumsum(counts, dim=0) - counts
+  num_chunks = int(chunk_off[k])
+  codes = torch.arange(k, device=device)
+  chunk_code = torch.repeat_interleave(codes, chunks_per, output_size=num_chunks)
+  chunk_begin = start[chunk_code] + (torch.arange(num_chunks, device=device) - chunk_off[chunk_code]) * chunk
+  rank = torch.empty((n,), dtype=torch.int64, device=device)
+  rank[order] = torch.arange(n, device=device)
+  i32 = lambda t: t.to(torch.int32).contiguous()
+  return CodedSHPlan(index=sh_index, order=i32(order), rank=i32(rank), chunk_code=i32(chunk_code),
+                     chunk_begin=i32(chunk_begin), chunk_off=i32(chunk_off), num_chunks=num_chunks, k=k)
+
+
+def _coded_bwd(plan: CodedSHPlan, degree: int, positions, cam, out, g_out, g_dc, g_codebook, tmp, nbytes):
+  return _lib.load().ms_sh_coded_bwd(_lib.ptr(positions), _lib.ptr(cam), _lib.ptr(out), _lib.ptr(g_out), _lib.ptr(plan.rank),
+                                     _lib.ptr(plan.chunk_begin), _lib.ptr(plan.chunk_off), plan.num_chunks, plan.n, plan.k,
+                                     degree, _lib.ptr(g_dc), _lib.ptr(g_codebook), _lib.ptr(tmp), ctypes.byref(nbytes),
+                                     None if out is None else _lib.current_stream(out.device))
+
+
+class _CodedSHFunction(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, dc, sh_codebook, positions, camera_pos, plan, degree):
+    dc_c, codebook_c = dc.detach().contiguous(), sh_codebook.detach().contiguous()
+    points_c, cam_c = positions.detach().contiguous(), camera_pos.detach().contiguous()
+    n = dc_c.shape[0]
+    out = torch.empty((n, 3), dtype=torch.float32, device=dc_c.device)
+    _lib.check(_lib.load().ms_sh_coded_fwd(dc_c.data_ptr(), plan.index.data_ptr(), codebook_c.data_ptr(), points_c.data_ptr(),
+                                           cam_c.data_ptr(), n, plan.k, degree, out.data_ptr(),
+                                           _lib.current_stream(dc_c.device)), "evaluate_sh_coded")
+    ctx.save_for_backward(points_c, cam_c, out)
+    ctx.plan, ctx.degree = plan, degree
+    ctx.codebook_shape = tuple(codebook_c.shape)
+    return out
+
+  @staticmethod
+  def backward(ctx, g_out):
+    points, cam, out = ctx.saved_tensors
+    plan, degree = ctx.plan, ctx.degree
+    need_dc, need_codebook = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if not (need_dc or need_codebook):
+      return (None,) * 6
+    g_out = g_out.contiguous()
+    g_dc = torch.empty_like(out) if need_dc else None
+    # every row is written, the rows of codes without members as zeros: no zero fill
+    g_codebook = torch.empty(ctx.codebook_shape, dtype=torch.float32, device=out.device) if need_codebook else None
+    if degree not in plan._scratch_bytes:
+      nbytes = ctypes.c_size_t(0)
+      _lib.check(_coded_bwd(plan, degree, None, None, None, None, None, None, None, nbytes), "evaluate_sh_coded backward")
+      plan._scratch_bytes[degree] = int(nbytes.value)
+    tmp = torch.empty((max(plan._scratch_bytes[degree], 1),), dtype=torch.uint8, device=out.device)
+    nbytes = ctypes.c_size_t(tmp.numel())
+    _lib.check(_coded_bwd(plan, degree, points, cam, out, g_out, g_dc, g_codebook, tmp, nbytes), "evaluate_sh_coded backward")
+    return g_dc, g_codebook, None, None, None, None
+
+
+def evaluate_sh_coded(dc: torch.Tensor,             # N, 3: the DC band
+                      sh_index: torch.Tensor,       # N int32 into sh_codebook
+                      sh_codebook: torch.Tensor,    # K, 3, (degree + 1)^2 - 1: the codes of the higher bands
+                      positions: torch.Tensor,      # N, 3
+                      camera_pos: torch.Tensor,     # 3
+                      *, plan: Optional[CodedSHPlan] = None) -> torch.Tensor:   # N, 3
+  """The colours ``evaluate_sh_at(cat(dc[:, :, None], sh_codebook[sh_index]), positions, arange(N), camera_pos)`` of a
+  vector-quantised scene (``scene_codec.CompressedScene``) without the decoded (N, 3, D) tensor, in storage order.
+  Gradients reach ``dc`` (dense) and ``sh_codebook`` (summed per code in float64 in an order fixed by ``sh_index``: no
+  atomics, two runs bitwise equal).  None reaches ``positions``, which the renderer detaches for SH as the reference
+  does; a ``camera_pos`` that requires grad is a ``NotImplementedError``.  ``plan`` is ``make_coded_sh_plan(sh_index, K)``;
+  ``None`` builds one (a sort and a host read: keep the plan while ``sh_index`` stays).  float32 on the GPU only."""
+  if camera_pos.requires_grad:
+    raise NotImplementedError("evaluate_sh_coded: no gradient with respect to camera_pos (detach it)")
+  floats = dict(dc=dc, sh_codebook=sh_codebook, positions=positions, camera_pos=camera_pos)
+  for name, t in floats.items():
+    if t.dtype != torch.float32:
+      raise ValueError(f"evaluate_sh_coded: {name} must be float32, got {t.dtype}")
+  if sh_index.dtype != torch.int32:
+    raise ValueError(f"evaluate_sh_coded: sh_index must be int32, got {sh_index.dtype}")
+  n = dc.shape[0]
+  if tuple(dc.shape) != (n, 3) or tuple(positions.shape) != (n, 3) or tuple(sh_index.shape) != (n,) or camera_pos.numel() != 3:
+    raise ValueError(f"evaluate_sh_coded: dc (N, 3), sh_index (N,), positions (N, 3), camera_pos (3,) expected, got "
+                     f"{tuple(dc.shape)}, {tuple(sh_index.shape)}, {tuple(positions.shape)}, {tuple(camera_pos.shape)}")
+  if sh_codebook.ndim != 3 or sh_codebook.shape[1] != 3 or sh_codebook.shape[2] not in (3, 8, 15) or not 1 <= sh_codebook.shape[0] <= 65536:
+    raise ValueError(f"evaluate_sh_coded: sh_codebook must be (K <= 65536, 3, 3 | 8 | 15), got {tuple(sh_codebook.shape)}")
+  _lib.require_gpu(dc, sh_index, sh_codebook, positions, camera_pos)
+  if len({t.device for t in (dc, sh_index, sh_codebook, positions, camera_pos)}) != 1:
+    raise ValueError("evaluate_sh_coded: the tensors are on different devices")
+  k, degree = sh_codebook.shape[0], {3: 1, 8: 2, 15: 3}[sh_codebook.shape[2]]
+  if plan is None:
+    plan = make_coded_sh_plan(sh_index, k)
+  elif plan.k != k or plan.n != n or plan.order.device != dc.device:
+    raise ValueError(f"evaluate_sh_coded: the plan is for N = {plan.n}, K = {plan.k} on {plan.order.device}")
+  if plan.index is not sh_index:      # a plan of other indices would still sum every product, under the wrong code
+    if plan.index.data_ptr() != sh_index.data_ptr() or plan.index.shape != sh_index.shape:
+      raise ValueError("evaluate_sh_coded: the plan was built from another sh_index tensor")
+  if not plan.index.is_contiguous():
+    raise ValueError("evaluate_sh_coded: sh_index must be contiguous")
+  return _CodedSHFunction.apply(dc, sh_codebook, positions, camera_pos, plan, degree)
 
 
 # ---- rotating the bands: Gaussians3D.transformed / ms_scene_transform (csrc/scene_transform.hip) ------------------------

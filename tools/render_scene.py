@@ -10,7 +10,7 @@ gaussians and tile overlaps; ms per frame is the median over the views after one
 --out the images are written as view_000.npy ... (H, W, 3) float32.
 
     python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d] [--transform "x 90 0.5"]
-                                           [--coverage] [--sh-codes K]
+                                           [--coverage] [--sh-codes K [--coded]]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 --transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
@@ -22,6 +22,9 @@ many gaussians are seen by no view, by some but not all (1..K-1), and by all K v
 iterations, seed 0), renders the decoded scene beside the original from every view and adds to the JSON line the two
 sizes in bytes, the time of the compression and the PSNR between the two renders (peak 1; per view and over all views).
 With --out the quantised images are written as quantised_000.npy ....
+--coded (with --sh-codes) also renders the quantised scene straight from its codebook (render_compressed: no decoded
+feature tensor) and adds the PSNR of that render against the decoded one (null when they are identical) and the median
+frame time of both, after one warm-up pass each.
 """
 import argparse
 import json
@@ -103,7 +106,38 @@ def coverage_report(gaussians, cameras, config):
   return report
 
 
-def quantised_report(gaussians, cameras, config, sh_codes, sh_degree, images, out):
+def timed_frames(render, cameras):
+  """median ms per frame of ``render(camera)`` over ``cameras`` after one warm-up pass, and the images of the timed pass"""
+  images, frame_ms = [], []
+  for camera in cameras:
+    render(camera)
+  torch.cuda.synchronize()
+  for camera in cameras:
+    begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    begin.record()
+    image = render(camera)
+    end.record()
+    end.synchronize()
+    frame_ms.append(begin.elapsed_time(end))
+    images.append(image)
+  return statistics.median(frame_ms), images
+
+
+def coded_report(scene, decoded, cameras, config, sh_degree):
+  """render_compressed beside render_gaussians(decode()): PSNR between the two and both frame times"""
+  from taichi_splatting_amd import render_compressed
+  with torch.no_grad():
+    decoded_ms, decoded_images = timed_frames(lambda cam: render_gaussians(decoded, cam, config, use_sh=True, sh_degree=sh_degree).image, cameras)
+    coded_ms, coded_images = timed_frames(lambda cam: render_compressed(scene, cam, config).image, cameras)
+  mean = statistics.fmean(float(((a.double() - b.double()) ** 2).mean()) for a, b in zip(coded_images, decoded_images))
+  report = dict(coded_psnr_db=round(-10.0 * math.log10(mean), 3) if mean > 0 else None,
+                coded_frame_ms=round(coded_ms, 4), decoded_frame_ms=round(decoded_ms, 4))
+  print(f"coded: {report['coded_frame_ms']} ms per frame from the codebook, {report['decoded_frame_ms']} ms decoded; PSNR between "
+        f"the two {report['coded_psnr_db']} dB", file=sys.stderr, flush=True)
+  return report
+
+
+def quantised_report(gaussians, cameras, config, sh_codes, sh_degree, images, out, coded=False):
   """compress_scene + decode, one render per camera beside ``images`` (the original's): sizes, seconds, PSNR"""
   from taichi_splatting_amd import compress_scene
   torch.cuda.synchronize()
@@ -125,6 +159,8 @@ def quantised_report(gaussians, cameras, config, sh_codes, sh_degree, images, ou
   mean = statistics.fmean(squared)
   report = dict(sh_codes=sh_codes, compress_s=round(seconds, 4), original_bytes=original_bytes, quantised_bytes=scene.nbytes,
                 psnr_db=round(-10.0 * math.log10(mean), 3) if mean > 0 else None, psnr_db_per_view=per_view)
+  if coded:
+    report.update(coded_report(scene, decoded, cameras, config, sh_degree))
   print(f"quantised: {sh_codes} codes in {seconds:.2f} s; {original_bytes} -> {scene.nbytes} bytes "
         f"({original_bytes / scene.nbytes:.2f} x); PSNR between the two renders {report['psnr_db']} dB", file=sys.stderr, flush=True)
   return report
@@ -145,7 +181,14 @@ def main():
                  help="before rendering, run camera_coverage over the orbit: time, and gaussians seen by 0, 1..K-1, all K views")
   p.add_argument('--sh-codes', type=int, default=None, metavar='K',
                  help="also render the scene with its higher SH bands quantised to a K-code codebook: sizes and PSNR")
+  p.add_argument('--coded', action='store_true',
+                 help="with --sh-codes: also render straight from the codebook (render_compressed); PSNR against the decoded "
+                      "render and both frame times")
   args = p.parse_args()
+  if args.coded and args.sh_codes is None:
+    sys.exit("render_scene: --coded needs --sh-codes")
+  if args.coded and args.sh_degree is not None:
+    sys.exit("render_scene: --coded renders every stored band: it does not combine with --sh-degree")
   try:
     transform = parse_transform(args.transform) if args.transform is not None else None
     if transform is not None:
@@ -200,7 +243,7 @@ def main():
   quantised = None
   if args.sh_codes is not None:
     try:
-      quantised = quantised_report(gaussians, cameras, config, args.sh_codes, args.sh_degree, images, args.out)
+      quantised = quantised_report(gaussians, cameras, config, args.sh_codes, args.sh_degree, images, args.out, coded=args.coded)
     except ValueError as e:
       sys.exit(f"render_scene: --sh-codes: {e}")
   print(json.dumps(dict(
