@@ -31,8 +31,11 @@ extern "C" {
  * ms_frame_desc with the caller's MS_VERSION) — every ms_frame_* call rejects a struct of another size or generation
  * with MS_ERR_ABI instead of reading fields that are not where it expects them (round 5 grew ms_frame_desc and
  * ms_frame_layout under version 400); split_min_run / split_seg_len parameters of the ms_raster_*_split functions,
- * ms_frame_desc.split_seg_len; ms_optim_* (fused optimiser groups). */
-#define MS_VERSION 500
+ * ms_frame_desc.split_seg_len; ms_optim_* (fused optimiser groups).
+ * 501 (0.5.1): the direct-order mapper has one construction — the two entry points of the u64-key form (emission of
+ * tile << 32 | depth key with int32 values, per-tile sort of such keys) are gone, ms_tile_payload_sort is the per-tile
+ * sort on its own.  No struct changed: the generation stays 5 and sized structs built against 500 are accepted. */
+#define MS_VERSION 501
 #define MS_ABI_GENERATION(version) ((version) / 100)
 
 enum { MS_F32 = 0, MS_F64 = 1 };
@@ -179,16 +182,6 @@ int ms_tile_emit(const float* points7, const float* depth, const int32_t* order,
                  int points_are_ordered /* points7 is ms_tile_count's ordered copy */,
                  void* out_keys, int32_t* out_values, void* stream);
 
-/* The same emission in storage order (no `order`) with the sort key of ms_depth_sort_keys fused in:
- * out_keys[o] = (tile_id << 32) | key32(depth[p]) — float bits of the depth, of its ndc value when ndc_near > 0
- * (torch_lib/projection.py:120-123), or the 16 bit quantisation when depth16 != 0 — and out_values[o] = p.  depth
- * is float or double (depth_dtype).  Feeds the direct-order mapper: ms_radix_sort_pairs on bits
- * [32, 32 + tile bits), ms_find_ranges(key_bytes 8, tile_shift 32), ms_tile_depth_sort. */
-int ms_tile_emit_keys64(const float* points7, const void* depth, int depth_dtype, const int32_t* cum, int64_t v,
-                        int image_w, int image_h, int tile_size, float alpha_threshold, int tile_row_begin,
-                        int tile_row_end, int depth16, double ndc_near, double ndc_far, uint64_t* out_keys,
-                        int32_t* out_values, void* stream);
-
 /* cuda_lib.radix_sort_pairs (cuda_lib/radix_sort_pairs.cu:8-70 = cub::DeviceRadixSort::SortPairs):
  * stable LSD radix sort of n (key, int32 value) pairs on key bits [begin_bit, end_bit),
  * out-of-place, inputs preserved.  key_bytes is 4 or 8 (unsigned order). */
@@ -210,22 +203,26 @@ int ms_segmented_sort_pairs(const int32_t* keys_in, const int32_t* values_in, in
 int ms_find_ranges(const void* sorted_keys, int64_t k, int key_bytes, int tile_shift,
                    int64_t num_tiles, int32_t* out_ranges, void* stream);
 
-/* Per-tile depth sort behind a tile-only sort (the frame executor's mapper, csrc/tile_sort.hip; together with a
- * stable sort of `tile << 32 | depth key` pairs on bits [32, 32 + tile_bits) it replaces the reference's 6-pass sort
- * of the whole 64 bit key, tile_mapper.py:148-170, and gives the same order).  sorted_keys (K) u64, grouped by tile
- * (bits 32..) with a 32 bit depth key below; overlap_to_point (K) the point indices, ascending inside every tile's run
- * — what a stable sort of a storage-order emission leaves; tile_ranges (num_tiles, 2) from
- * ms_find_ranges(key_bytes 8, tile_shift 32).  On return every run of overlap_to_point is in (depth key, point index)
- * order.  sorted_keys is scratch afterwards (long runs are sorted through it); `scratch`: K more u64 words. */
-int ms_tile_depth_sort(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_keys,
-                       int32_t* overlap_to_point, uint64_t* scratch, void* stream);
+/* Per-tile depth sort behind a tile-only sort (the last stage of the direct-order mapper, csrc/tile_sort.hip;
+ * together with a stable sort of the overlaps on their tile id alone it replaces the reference's 6-pass sort of the
+ * whole 64 bit key, tile_mapper.py:148-170, and gives the same order).  payload (K) u64 words
+ * key32(depth) << 32 | point index, grouped by tile; tile_ranges (num_tiles, 2): the [first, last + 1) run of each
+ * tile.  On return every run of out_overlap_to_point (K) holds the run's point indices in (depth key, point index)
+ * order, the order of the payload words themselves.  out_overlap_to_point is output only and every entry inside a
+ * range is written: a run of one entry, or of one depth key, has no order to find but is still copied out.  `payload`
+ * is scratch afterwards (long runs are sorted through it); `scratch`: K more u64 words. */
+int ms_tile_payload_sort(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* payload,
+                         int32_t* out_overlap_to_point, uint64_t* scratch, void* stream);
 
-/* The frame executor's direct-order mapper on its own, from the scanned overlap counts to the lists: the launch
- * sequence ms_frame_map_raster runs when ms_frame_desc.mapper is MS_MAPPER_DIRECT, with no host read in it.  The
- * overlaps are emitted in storage order as two streams — tile ids of 2 bytes (4 when the image has more than 65 536
- * tiles) and payload words key32(depth) << 32 | point index (key32 as in ms_tile_emit_keys64) — sorted by tile id with
- * the stable radix passes of ms_radix_sort_pairs, ranged, and every tile's run of payload words is sorted as it is.
- * Same lists as ms_tile_emit_keys64 -> ms_radix_sort_pairs -> ms_find_ranges -> ms_tile_depth_sort.
+/* The direct-order mapper, from the scanned overlap counts to the lists, with no host read in it: the launch sequence
+ * ms_frame_map_raster runs when ms_frame_desc.mapper is MS_MAPPER_DIRECT and map_to_tiles(method='direct') runs on its
+ * own.  The overlaps are emitted in storage order as two streams — tile ids of 2 bytes (4 when the image has more than
+ * 65 536 tiles) and payload words key32(depth) << 32 | point index — sorted by tile id with the stable radix passes of
+ * ms_radix_sort_pairs, ranged, and every tile's run of payload words is sorted as it is (ms_tile_payload_sort).
+ * key32 is the sort key of ms_depth_sort_keys: float bits of the depth, of its ndc value when ndc_near > 0
+ * (torch_lib/projection.py:120-123), or the 16 bit quantisation when depth16 != 0; depth is float or double
+ * (depth_dtype).  The lists are in (tile, key32, point index) order: those of the reference's sort of the whole key
+ * (tile_mapper.py:148-170) with ties in point order.
  * points7 (v, 7) float; cum (v + 1) from ms_exclusive_scan_i32 over the counts of ms_tile_count (a gaussian whose
  * count is zero emits nothing); image_w / image_h padded to the tile size.  k_capacity: entries of
  * out_overlap_to_point.  out_tile_ranges (tiles, 2), written whole.  out_counters: 8 int32 on the device —

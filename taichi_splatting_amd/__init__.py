@@ -26,7 +26,7 @@ from .misc.kmeans import kmeans, kmeans_assign, kmeans_update, KMeansResult
 from .scene_codec import compress_scene, load_compressed, CompressedScene, render_compressed
 from .spherical_harmonics import evaluate_sh_coded, make_coded_sh_plan, CodedSHPlan
 
-__version__ = '0.5.0'       # = MS_VERSION 500 of include/mi355_splat.h (tests/test_abi.py holds the two together)
+__version__ = '0.5.1'       # = MS_VERSION 501 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
 __all__ = [
   'render_gaussians', 'Rendering',

@@ -23,7 +23,7 @@ MS_F32, MS_F64 = 0, 1
 BACKWARD_ALL, BACKWARD_GAUSSIANS, BACKWARD_RASTER = 0, 1, 2   # ms_frame_grads.stage
 BOUNDARY_AXIS_SIGMA, BOUNDARY_COVARIANCE = 0, 1
 MAPPER_DIRECT, MAPPER_PRESORT = 0, 1               # ms_frame_grads.boundary_form
-ABI_VERSION = 500  # MS_VERSION of include/mi355_splat.h this binding was written against (tests/test_abi.py)
+ABI_VERSION = 501  # MS_VERSION of include/mi355_splat.h this binding was written against (tests/test_abi.py)
 PAD_SAME, PAD_VALID = 0, 1                         # MS_PAD_SAME / MS_PAD_VALID (ms_photometric_*)
 MOMENT_ROW = 16   # MS_MOMENT_ROW of include/mi355_splat.h
 SPLAT_ROW = 16    # MS_SPLAT_ROW
@@ -162,12 +162,11 @@ SIGNATURES = {
   'ms_depth_sort_keys': (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_void_p, c_void_p, c_int, c_void_p]),
   'ms_depth_argsort': (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
   'ms_exclusive_scan_i32': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
-  'ms_tile_emit_keys64': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
   'ms_tile_emit': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
   'ms_radix_sort_pairs': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int, c_void_p, POINTER(c_size_t), c_void_p]),
   'ms_segmented_sort_pairs': (c_int, [c_void_p] * 4 + [c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
   'ms_find_ranges': (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p]),
-  'ms_tile_depth_sort': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+  'ms_tile_payload_sort': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
   'ms_map_tiles_direct': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
                                   c_double, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
   'ms_fractional_step': (c_int, [c_int, c_int] + [c_void_p] * 7 + [c_int64, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p]),

@@ -85,33 +85,25 @@ void tile_emit_ordered_launch(const float* ordered_points7, const int32_t* order
                               int row_end, const int32_t* k_limit_dev, uint32_t* out_keys, int32_t* out_values,
                               hipStream_t s);
 
-// direct-order mapper of the frame executor (no depth pre-sort): overlap counts in storage order (cull_depth: rows
-// with depth <= 0 overlap nothing), then u64 keys tile << 32 | depth_sort_key and the point index as value
+// direct-order mapper (no depth pre-sort): overlap counts in storage order (cull_depth: rows with depth <= 0 overlap
+// nothing), then the emission as two streams, tile ids (id_bytes: tile_id_bytes of the launch) and payload words
+// depth_sort_key << 32 | point index; nothing is written when *k_limit_dev == 0
 void tile_count_direct_launch(const float* points7, const void* cull_depth, int dtype, int64_t v, int image_w, int image_h,
                               int tile_size, float alpha_threshold, int row_begin, int row_end, int32_t* out_counts,
                               hipStream_t s);
-void tile_emit_direct_launch(const float* points7, const void* depth, int dtype, const int32_t* cum, int64_t v, int image_w,
-                             int image_h, int tile_size, float alpha_threshold, int row_begin, int row_end, int depth16,
-                             double ndc_near, double ndc_far, const int32_t* k_limit_dev, uint64_t* out_keys,
-                             int32_t* out_values, hipStream_t s);
-
-// the two-stream form of the emission (id_bytes: tile_id_bytes of the launch)
 void tile_emit_ids_launch(const float* points7, const void* depth, int dtype, const int32_t* cum, int64_t v, int image_w,
                           int image_h, int tile_size, float alpha_threshold, int row_begin, int row_end, int depth16,
                           double ndc_near, double ndc_far, const int32_t* k_limit_dev, int id_bytes, void* out_tiles,
                           uint64_t* out_payload, hipStream_t s);
 
 // ---- tile_sort.hip ----------------------------------------------------------------------------------------------
-// Sorts every tile's run of `sorted_keys` (tile << 32 | depth key, already grouped by tile with the point indices in
-// `overlap_to_point` ascending inside each run) by (depth key, point index); only overlap_to_point is rewritten.
-// `scratch`: K u64 words the large-tile path may use (the unsorted key buffer is free by then).
+// Sorts every tile's run of `sorted_payload` (payload words depth key << 32 | point index, already grouped by tile)
+// by the word itself, that is by (depth key, point index), and writes the point indices of the sorted runs to
+// overlap_to_point (output only; a run of one entry is copied out).  sorted_payload is scratch afterwards; `scratch`:
+// K more u64 words the large-tile path may use (the sort's other payload buffer is free by then).
 // run_stats (device, three zeroed words, or NULL): [2] = "a per-tile kernel declined a run" (NULL: the long-run kernel
 // reads every run's mark; [0], [1] unused).  run_host (pinned, may be NULL) receives the length of a run above 16384
 // entries if there is one.
-void tile_depth_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_keys, int32_t* overlap_to_point,
-                            uint64_t* scratch, hipStream_t s, int32_t* run_stats = nullptr, int32_t* run_host = nullptr);
-
-// The same on runs of payload words depth key << 32 | point index (grouped by tile): overlap_to_point is output only.
 void tile_payload_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_payload, int32_t* overlap_to_point,
                               uint64_t* scratch, hipStream_t s, int32_t* run_stats = nullptr, int32_t* run_host = nullptr);
 

@@ -204,36 +204,11 @@ tile_count_direct_kernel(const float* __restrict__ points, const T* __restrict__
   if (i < v) counts[i] = count;
 }
 
-// key = tile_id << 32 | depth_sort_key(depth) (the 32 bit key of the depth pre-sort), value = point index
-template <typename T>
-__global__ void __launch_bounds__(256)
-tile_emit_direct_kernel(const float* __restrict__ points, const T* __restrict__ depth, const int32_t* __restrict__ cum,
-                        int64_t v, int image_w, int image_h, int tile_size, float alpha_threshold, int row_begin,
-                        int row_end, int depth16, double near_plane, double far_plane,
-                        const int32_t* __restrict__ k_limit, uint64_t* __restrict__ keys, int32_t* __restrict__ values) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k_limit && *k_limit == 0) return;                // overflow of the caller's capacity: write nothing (uniform)
-  const int64_t first = i < v ? (int64_t)cum[i] : 0;
-  const bool valid = i < v && cum[i + 1] != first;     // not culled, and overlaps a tile of this strip
-  float g[7] = {0.f, 0.f, 1.f, 0.f, 1.f, 1.f, 0.f};
-  if (valid) load_point7(points, i, g);
-  const ObbQuery q = obb_grid_query(g, image_w, image_h, tile_size, alpha_threshold);
-  const int tiles_wide = image_w / tile_size;
-  const uint32_t depth_key = valid ? (uint32_t)depth_sort_key(depth[i], depth16, near_plane, far_plane) : 0u;
-  emit_span(q, valid, first, tile_size, row_begin, row_end, [&](int64_t o, int tx, int ty, int from) {
-    const uint64_t tile_id = (uint64_t)((int64_t)tx + (int64_t)ty * tiles_wide);
-    uint32_t dk = depth_key;
-    int32_t who = (int32_t)i;
-    if (from >= 0) { dk = (uint32_t)__builtin_amdgcn_readlane((int)depth_key, from); who = __builtin_amdgcn_readlane((int32_t)i, from); }
-    keys[o] = (tile_id << 32) | dk;
-    values[o] = who;
-  });
-}
-
-// The same emission as two streams: tiles[o] = tile id (u16 while the launch has at most 65 536 tiles, u32 beyond) and
-// payload[o] = depth_sort_key(depth) << 32 | point index.  The stable sort on the tile bits then reads and moves 2 + 8
-// bytes per overlap instead of 8 + 4 and its histograms read the ids alone; the per-tile depth sort ranks the payload
-// words as they are (tile_sort.hip).
+// The emission as two streams: tiles[o] = tile id (u16 while the launch has at most 65 536 tiles, u32 beyond) and
+// payload[o] = depth_sort_key(depth) << 32 | point index — the sort key is tile_id, then depth_sort_key(depth) (the
+// 32 bit key of the depth pre-sort), then the point index.  The stable sort on the tile bits reads and moves 2 + 8
+// bytes per overlap and its histograms read the ids alone; the per-tile depth sort ranks the payload words as they are
+// (tile_sort.hip).
 template <typename T, typename IdT>
 __global__ void __launch_bounds__(256)
 tile_emit_ids_kernel(const float* __restrict__ points, const T* __restrict__ depth, const int32_t* __restrict__ cum,
@@ -297,21 +272,6 @@ void tile_count_direct_launch(const float* points7, const void* cull_depth, int 
   else
     tile_count_direct_kernel<float><<<grid, block, 0, s>>>(points7, (const float*)cull_depth, v, image_w, image_h, tile_size,
                                                            alpha_threshold, row_begin, row_end, out_counts);
-}
-
-void tile_emit_direct_launch(const float* points7, const void* depth, int dtype, const int32_t* cum, int64_t v, int image_w,
-                             int image_h, int tile_size, float alpha_threshold, int row_begin, int row_end, int depth16,
-                             double ndc_near, double ndc_far, const int32_t* k_limit_dev, uint64_t* out_keys,
-                             int32_t* out_values, hipStream_t s) {
-  const dim3 grid((unsigned)div_up(v, 256)), block(256);
-  if (dtype == MS_F64)
-    tile_emit_direct_kernel<double><<<grid, block, 0, s>>>(points7, (const double*)depth, cum, v, image_w, image_h, tile_size,
-                                                           alpha_threshold, row_begin, row_end, depth16, ndc_near, ndc_far,
-                                                           k_limit_dev, out_keys, out_values);
-  else
-    tile_emit_direct_kernel<float><<<grid, block, 0, s>>>(points7, (const float*)depth, cum, v, image_w, image_h, tile_size,
-                                                          alpha_threshold, row_begin, row_end, depth16, ndc_near, ndc_far,
-                                                          k_limit_dev, out_keys, out_values);
 }
 
 void tile_emit_ids_launch(const float* points7, const void* depth, int dtype, const int32_t* cum, int64_t v, int image_w,
@@ -380,27 +340,6 @@ extern "C" int ms_tile_emit(const float* points7, const float* depth, const int3
   else if (key_mode == 1) MS_EMIT(uint32_t, 1);
   else MS_EMIT(uint32_t, 2);
 #undef MS_EMIT
-  MS_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int ms_tile_emit_keys64(const float* points7, const void* depth, int depth_dtype, const int32_t* cum, int64_t v,
-                                   int image_w, int image_h, int tile_size, float alpha_threshold, int tile_row_begin,
-                                   int tile_row_end, int depth16, double ndc_near, double ndc_far, uint64_t* out_keys,
-                                   int32_t* out_values, void* stream) {
-  MS_CHECK_ARG(v >= 0, "v < 0");
-  MS_CHECK_ARG(depth_dtype == MS_F32 || depth_dtype == MS_F64, "depth_dtype must be MS_F32 or MS_F64");
-  MS_CHECK_ARG(tile_size > 0 && image_w > 0 && image_h > 0, "bad image/tile size");
-  MS_CHECK_ARG(image_w % tile_size == 0 && image_h % tile_size == 0, "image size must be padded to the tile size");
-  if (depth16) {
-    const int64_t tiles = (int64_t)(image_w / tile_size) * (image_h / tile_size);
-    MS_CHECK_ARG(tiles <= 65536, "use_depth16 keys hold a 16 bit tile id: too many tiles");   // tile_mapper.py:49-53
-  }
-  if (v == 0) return 0;
-  MS_CHECK_ARG(points7 && depth && cum && out_keys && out_values, "null pointer");
-  tile_emit_direct_launch(points7, depth, depth_dtype, cum, v, image_w, image_h, tile_size, alpha_threshold, tile_row_begin,
-                          tile_row_end, depth16, ndc_near > 0.0 ? ndc_near : 0.0, ndc_far, nullptr, out_keys, out_values,
-                          (hipStream_t)stream);
   MS_CHECK_LAUNCH();
   return 0;
 }

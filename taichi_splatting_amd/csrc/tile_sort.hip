@@ -1,11 +1,12 @@
-// tile_sort.hip — per-tile depth sort of the frame executor's direct-order mapper.
+// tile_sort.hip — per-tile depth sort of the direct-order mapper.
 //
 // The reference sorts ONE array of 64 bit keys tile << 32 | depth bits (mapper/tile_mapper.py:36-42, 148-170: a full
-// radix sort over K overlaps); the round-2/3 frame executor pre-sorted the gaussians by depth and sorted the overlaps by
-// tile only.  Here the overlaps are emitted in storage order, grouped by tile with a stable sort on the tile bits alone
-// (scan_sort.hip), and every tile's run — a few hundred to a few thousand entries that one workgroup holds in LDS — is
-// put into (depth key, point index) order by this kernel.  The order that results is the reference's: equal depth
-// keys keep ascending point indices, which is what a stable sort of the storage-order emission gives.
+// radix sort over K overlaps); the pre-sort mapper sorts the gaussians by depth and the overlaps by tile only.  Here the
+// overlaps are emitted in storage order as narrow tile ids next to payload words depth key << 32 | point index, grouped
+// by tile with a stable sort on the ids alone (scan_sort.hip), and every tile's run — a few hundred to a few thousand
+// entries that one workgroup holds in LDS — is put into (depth key, point index) order by this kernel.  The order that
+// results is the reference's: equal depth keys keep ascending point indices.  The payload word is exactly what the runs
+// are ranked by, so 8 bytes are read per entry and overlap_to_point is only written.
 //
 // One workgroup per tile.  Runs up to 256 * R entries: a bucket sort in LDS — min / max of the run's keys, a MONOTONE
 // map of the key onto as many buckets as there are entries (by float value for normal positive float keys, so that
@@ -14,11 +15,6 @@
 // that precede it in (key, index) order.  Anything else — longer runs, or runs whose keys pile up in few buckets (sum
 // of squared bucket sizes above TS_COST_LIMIT per entry) — goes through an LSD radix sort of the workgroup on global
 // memory that skips the digits that do not vary: slower per entry but bounded, so no input makes this kernel quadratic.
-//
-// Two input forms (PAYLOAD).  false (ms_tile_depth_sort): the sorted keys tile << 32 | depth key with the point indices
-// in overlap_to_point, 12 bytes read per entry.  true (the frame executor): the run is ONE array of payload words
-// depth key << 32 | point index, grouped by tile through a sort of narrow tile ids (scan_sort.hip) — exactly the word
-// both paths rank by, so 8 bytes are read per entry and overlap_to_point is only written.
 #include "common.h"
 #include "frame_internal.h"
 
@@ -88,22 +84,14 @@ __device__ __forceinline__ uint32_t ts_block_exclusive(uint32_t v, uint32_t* red
 }
 
 // ---- bounded path: LSD radix sort of one run by the whole workgroup, on global memory ------------------------------
-// srt[b .. b + n): tile << 32 | depth key; o2p[b .. b + n): point indices (ascending); alt: scratch of the same extent.
+// srt[b .. b + n): depth key << 32 | point index; o2p[b .. b + n): output only; alt: scratch of the same extent.
 // wcnt: TS_WAVES * 256 words of LDS (per-wave digit counters, then write positions)
-// PAYLOAD: srt[b .. b + n) holds depth key << 32 | point index already and o2p is output only
-template <bool PAYLOAD>
 __device__ void tile_radix_sort_global(uint64_t* srt, int32_t* o2p, uint64_t* alt,
                                        int64_t b, int n, TsShared& sh, uint32_t* wcnt) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   uint32_t kor = 0u, kand = 0xffffffffu;
   for (int i = t; i < n; i += TS_THREADS) {
-    uint32_t k;
-    if constexpr (PAYLOAD) {
-      k = (uint32_t)(srt[b + i] >> 32);
-    } else {
-      k = (uint32_t)srt[b + i];
-      srt[b + i] = ((uint64_t)k << 32) | (uint32_t)o2p[b + i];
-    }
+    const uint32_t k = (uint32_t)(srt[b + i] >> 32);
     kor |= k;
     kand &= k;
   }
@@ -179,7 +167,6 @@ __device__ void tile_radix_sort_global(uint64_t* srt, int32_t* o2p, uint64_t* al
     uint64_t* const swap = src; src = dst; dst = swap;
   }
   __syncthreads();
-  if (!PAYLOAD && src == srt && vary == 0u) return;              // nothing moved
   for (int i = t; i < n; i += TS_THREADS) o2p[b + i] = (int32_t)(uint32_t)src[b + i];
 }
 
@@ -196,7 +183,7 @@ struct BucketMap {
 };
 
 // false: declined (nothing written) — the keys pile up in few buckets and the run belongs to the bounded path
-template <int R, bool PAYLOAD>
+template <int R>
 __device__ __forceinline__ bool tile_bucket_sort(uint64_t* __restrict__ srt, int32_t* __restrict__ o2p,
                                                  int64_t b, int n, uint64_t* pairs, uint32_t* cnt, TsShared& sh) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -207,14 +194,9 @@ __device__ __forceinline__ bool tile_bucket_sort(uint64_t* __restrict__ srt, int
     const int i = t + TS_THREADS * r;
     key[r] = 0u; id[r] = 0u;
     if (i < n) {
-      if constexpr (PAYLOAD) {
-        const uint64_t p = srt[b + i];
-        key[r] = (uint32_t)(p >> 32);
-        id[r] = (uint32_t)p;
-      } else {
-        key[r] = (uint32_t)srt[b + i];
-        id[r] = (uint32_t)o2p[b + i];
-      }
+      const uint64_t p = srt[b + i];
+      key[r] = (uint32_t)(p >> 32);
+      id[r] = (uint32_t)p;
       kmin = key[r] < kmin ? key[r] : kmin;
       kmax = key[r] > kmax ? key[r] : kmax;
     }
@@ -229,11 +211,9 @@ __device__ __forceinline__ bool tile_bucket_sort(uint64_t* __restrict__ srt, int
     kmax = sh.red[TS_WAVES + w] > kmax ? sh.red[TS_WAVES + w] : kmax;
   }
   if (kmin == kmax) {                      // one depth key: the run is in point order already
-    if constexpr (PAYLOAD) {
 #pragma unroll
-      for (int r = 0; r < R; ++r)
-        if (t + TS_THREADS * r < n) o2p[b + t + TS_THREADS * r] = (int32_t)id[r];
-    }
+    for (int r = 0; r < R; ++r)
+      if (t + TS_THREADS * r < n) o2p[b + t + TS_THREADS * r] = (int32_t)id[r];
     return true;
   }
 
@@ -302,10 +282,10 @@ __device__ __forceinline__ bool tile_bucket_sort(uint64_t* __restrict__ srt, int
 
 // One workgroup per tile (runs of lo < n <= hi <= 256 * R entries; the others belong to the kernel below).  Leaves
 // alt[b] = TS_DECLINED for a run it does not sort, 0 otherwise.
-template <int R, bool PAYLOAD>
-__device__ __forceinline__ void tile_depth_sort_body(const int32_t* __restrict__ ranges, uint64_t* __restrict__ srt,
-                                                     int32_t* __restrict__ o2p, uint64_t* __restrict__ alt, int lo, int hi,
-                                                     int32_t* __restrict__ run_stats) {
+template <int R>
+__global__ void __launch_bounds__(TS_THREADS, R <= 4 ? 8 : 1)
+tile_payload_sort_kernel(const int32_t* __restrict__ ranges, uint64_t* __restrict__ srt, int32_t* __restrict__ o2p,
+                         uint64_t* __restrict__ alt, int lo, int hi, int32_t* __restrict__ run_stats) {
   constexpr int CAP = TS_THREADS * R;
   __shared__ uint64_t pairs[CAP];          // key << 32 | point index, grouped by bucket
   __shared__ uint32_t cnt[CAP];            // bucket sizes, then bucket offsets
@@ -313,35 +293,22 @@ __device__ __forceinline__ void tile_depth_sort_body(const int32_t* __restrict__
   const int64_t tile = blockIdx.x;
   const int64_t b = ranges[2 * tile];
   const int n = ranges[2 * tile + 1] - (int32_t)b;
-  if (n <= lo || n > hi) return;           // lo >= 1: a single entry is sorted (PAYLOAD: lo >= 0, it is still copied out)
-  const bool sorted = tile_bucket_sort<R, PAYLOAD>(srt, o2p, b, n, pairs, cnt, sh);
+  if (n <= lo || n > hi) return;           // lo >= 0: a run of one entry has no order to find, but it is still copied out
+  const bool sorted = tile_bucket_sort<R>(srt, o2p, b, n, pairs, cnt, sh);
   if (threadIdx.x == 0) {
     alt[b] = sorted ? 0ull : TS_DECLINED;
     if (!sorted && run_stats) atomicOr(run_stats + 2, 1);          // tells the long-run kernel to look for the marks
   }
 }
 
-template <int R>
-__global__ void __launch_bounds__(TS_THREADS, R <= 4 ? 8 : 1)
-tile_depth_sort_kernel(const int32_t* __restrict__ ranges, uint64_t* __restrict__ srt, int32_t* __restrict__ o2p,
-                       uint64_t* __restrict__ alt, int lo, int hi, int32_t* __restrict__ run_stats) {
-  tile_depth_sort_body<R, false>(ranges, srt, o2p, alt, lo, hi, run_stats);
-}
-template <int R>
-__global__ void __launch_bounds__(TS_THREADS, R <= 4 ? 8 : 1)
-tile_payload_sort_kernel(const int32_t* __restrict__ ranges, uint64_t* __restrict__ payload, int32_t* __restrict__ o2p,
-                         uint64_t* __restrict__ alt, int lo, int hi, int32_t* __restrict__ run_stats) {
-  tile_depth_sort_body<R, true>(ranges, payload, o2p, alt, lo, hi, run_stats);
-}
-
 // The long runs (n > lo) and the declined ones: 60 KB of LDS per workgroup, so the grid is a few workgroups per CU and
 // each takes a contiguous share of the tiles — one thread looks at one tile's run, the workgroup then sorts the ones
 // that are its business: in LDS up to 256 * R entries, by the bounded path beyond (or when declined).
-template <int R, bool PAYLOAD>
-__device__ __forceinline__ void tile_depth_sort_long_body(const int32_t* __restrict__ ranges, int64_t num_tiles,
-                                                          uint64_t* __restrict__ srt, int32_t* __restrict__ o2p,
-                                                          uint64_t* __restrict__ alt, int lo, int32_t* __restrict__ run_stats,
-                                                          int32_t* __restrict__ run_host) {
+template <int R>
+__global__ void __launch_bounds__(TS_THREADS)
+tile_payload_sort_long_kernel(const int32_t* __restrict__ ranges, int64_t num_tiles, uint64_t* __restrict__ srt,
+                              int32_t* __restrict__ o2p, uint64_t* __restrict__ alt, int lo, int32_t* __restrict__ run_stats,
+                              int32_t* __restrict__ run_host) {
   constexpr int CAP = TS_THREADS * R;
   static_assert(CAP >= TS_WAVES * 256, "the bucket counters double as the bounded path's digit counters");
   __shared__ uint64_t pairs[CAP];
@@ -377,42 +344,14 @@ __device__ __forceinline__ void tile_depth_sort_long_body(const int32_t* __restr
       const int64_t b = ranges[2 * tile];
       const int n = ranges[2 * tile + 1] - (int32_t)b;
       bool sorted = false;
-      if (n <= CAP && !(entry >> 30)) sorted = tile_bucket_sort<R, PAYLOAD>(srt, o2p, b, n, pairs, cnt, sh);
+      if (n <= CAP && !(entry >> 30)) sorted = tile_bucket_sort<R>(srt, o2p, b, n, pairs, cnt, sh);
       if (!sorted) {
         __syncthreads();
-        tile_radix_sort_global<PAYLOAD>(srt, o2p, alt, b, n, sh, cnt);
+        tile_radix_sort_global(srt, o2p, alt, b, n, sh, cnt);
       }
       __syncthreads();                     // done with the shared arrays before the next run
     }
   }
-}
-
-template <int R>
-__global__ void __launch_bounds__(TS_THREADS)
-tile_depth_sort_long_kernel(const int32_t* __restrict__ ranges, int64_t num_tiles, uint64_t* __restrict__ srt,
-                            int32_t* __restrict__ o2p, uint64_t* __restrict__ alt, int lo, int32_t* __restrict__ run_stats,
-                            int32_t* __restrict__ run_host) {
-  tile_depth_sort_long_body<R, false>(ranges, num_tiles, srt, o2p, alt, lo, run_stats, run_host);
-}
-template <int R>
-__global__ void __launch_bounds__(TS_THREADS)
-tile_payload_sort_long_kernel(const int32_t* __restrict__ ranges, int64_t num_tiles, uint64_t* __restrict__ payload,
-                              int32_t* __restrict__ o2p, uint64_t* __restrict__ alt, int lo, int32_t* __restrict__ run_stats,
-                              int32_t* __restrict__ run_host) {
-  tile_depth_sort_long_body<R, true>(ranges, num_tiles, payload, o2p, alt, lo, run_stats, run_host);
-}
-
-void tile_depth_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_keys, int32_t* overlap_to_point,
-                            uint64_t* scratch, hipStream_t s, int32_t* run_stats, int32_t* run_host) {
-  if (num_tiles <= 0) return;
-  const dim3 per_tile((unsigned)num_tiles), block(TS_THREADS);
-  tile_depth_sort_kernel<SMALL_R><<<per_tile, block, 0, s>>>(tile_ranges, sorted_keys, overlap_to_point, scratch, 1,
-                                                            TS_THREADS * SMALL_R, run_stats);
-  tile_depth_sort_kernel<MID_R><<<per_tile, block, 0, s>>>(tile_ranges, sorted_keys, overlap_to_point, scratch,
-                                                          TS_THREADS * SMALL_R, TS_THREADS * MID_R, run_stats);
-  const int64_t few = 2 * 256;             // two workgroups of the long-run kernel fit a CU
-  tile_depth_sort_long_kernel<LONG_R><<<dim3((unsigned)(num_tiles < few ? num_tiles : few)), block, 0, s>>>(
-      tile_ranges, num_tiles, sorted_keys, overlap_to_point, scratch, TS_THREADS * MID_R, run_stats, run_host);
 }
 
 void tile_payload_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_payload, int32_t* overlap_to_point,
@@ -433,12 +372,12 @@ void tile_payload_sort_launch(const int32_t* tile_ranges, int64_t num_tiles, uin
 
 using namespace ms;
 
-extern "C" int ms_tile_depth_sort(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* sorted_keys,
-                                  int32_t* overlap_to_point, uint64_t* scratch, void* stream) {
+extern "C" int ms_tile_payload_sort(const int32_t* tile_ranges, int64_t num_tiles, uint64_t* payload,
+                                    int32_t* out_overlap_to_point, uint64_t* scratch, void* stream) {
   MS_CHECK_ARG(num_tiles >= 0 && num_tiles < (1ll << 31), "num_tiles out of range");
   if (num_tiles == 0) return 0;
-  MS_CHECK_ARG(tile_ranges && sorted_keys && overlap_to_point && scratch, "null pointer");
-  tile_depth_sort_launch(tile_ranges, num_tiles, sorted_keys, overlap_to_point, scratch, (hipStream_t)stream);
+  MS_CHECK_ARG(tile_ranges && payload && out_overlap_to_point && scratch, "null pointer");
+  tile_payload_sort_launch(tile_ranges, num_tiles, payload, out_overlap_to_point, scratch, (hipStream_t)stream, nullptr, nullptr);
   MS_CHECK_LAUNCH();
   return 0;
 }

@@ -1,13 +1,20 @@
 """Tile mapper: which gaussians touch which screen tiles, depth sorted per tile.
 
 Same interface as reference ``mapper/tile_mapper.py:204-225`` (``map_to_tiles``) and ``:20-24``
-(``pad_to_tile``).  Stages (csrc/mapper.hip, csrc/scan_sort.hip):
-depth pre-sort of the V gaussians (stable radix sort of the 32 bit depth keys) -> OBB-vs-tile overlap
-count in depth order -> exclusive scan (one host read of the total K) -> emission of (tile id, point)
--> stable radix sort on the ceil(log2 T) tile-id bits -> per-tile ranges.  The result is the order
-of the reference's single 48-bit sort of ``tile_id << 32 | float_bits(depth)`` keys generated in
-point order (tile, depth bits, point index) at a third of the sorted bytes.  Unlike the reference (``tile_mapper.py:177-178``) the tile id is not limited to
-16 bits, so 2048x2048 @ tile 8 and 4096x4096 @ tile 16 (65536 tiles) work.
+(``pad_to_tile``).  Two sequences of stages (csrc/mapper.hip, csrc/scan_sort.hip, csrc/tile_sort.hip), both with one
+host read of the overlap total K:
+
+* presort: depth pre-sort of the V gaussians (stable radix sort of the 32 bit depth keys) -> OBB-vs-tile overlap
+  count in depth order -> exclusive scan -> emission of (tile id, point) -> stable radix sort on the ceil(log2 T)
+  tile-id bits -> per-tile ranges;
+* direct: overlap count in storage order -> exclusive scan -> ``ms_map_tiles_direct``, the sequence the frame executor
+  runs: emission of (tile id, ``depth key << 32 | point``) -> stable radix sort on the tile ids -> per-tile ranges ->
+  every tile's run sorted by its payload words.
+
+Either result is the order of the reference's single 48-bit sort of ``tile_id << 32 | float_bits(depth)`` keys
+generated in point order (tile, depth bits, point index) at a fraction of the sorted bytes.  Unlike the reference
+(``tile_mapper.py:177-178``) the tile id is not limited to 16 bits, so 2048x2048 @ tile 8 and 4096x4096 @ tile 16
+(65536 tiles) work.
 """
 from __future__ import annotations
 
@@ -41,7 +48,9 @@ def map_to_tiles_strip(gaussians: torch.Tensor, depth: torch.Tensor,
                        method: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
   """``map_to_tiles`` restricted to tile rows [tile_rows[0], tile_rows[1]) (multi-GPU strips).
 
-  ``method``: ``'direct'`` (storage-order emission, stable sort on the tile bits, per-tile depth sort) or
+  ``method``: ``'direct'`` (the frame executor's sequence, ``ms_map_tiles_direct``: storage-order emission of 2-byte
+  tile ids — 4 bytes beyond 65 536 tiles — and 8-byte ``depth key << 32 | point`` payloads, stable sort on the ids,
+  per-tile sort of the payload runs) or
   ``'presort'`` (gaussians sorted by depth first, overlaps sorted by tile id) — two constructions of the SAME lists
   (tile, depth key, point index); ``None`` picks by overlaps per gaussian (``PRESORT_ABOVE``), which is known here
   before anything is emitted.  ``'direct'`` sorts a tile run beyond 5120 entries with one workgroup (~12 ns per entry):
@@ -133,20 +142,18 @@ def map_to_tiles_strip(gaussians: torch.Tensor, depth: torch.Tensor,
         method = 'presort' if total > PRESORT_ABOVE * v else 'direct'      # presort: counted again below, in depth order
 
     if method == 'direct':
-      # 2. keys tile << 32 | depth key (ndc / 16 bit quantisation fused) in storage order; 3. STABLE sort on the tile
-      #    bits only: every tile's run keeps ascending point indices; 4. ranges; 5. each run sorted by (depth key,
-      #    point index) by one workgroup (csrc/tile_sort.hip).  Same lists as the full 64 bit sort, 2 passes over K.
-      keys = torch.empty((total,), dtype=torch.int64, device=device)
-      values = torch.empty((total,), dtype=torch.int32, device=device)
-      _lib.check(lib.ms_tile_emit_keys64(points.data_ptr(), depths.data_ptr(), _lib.dtype_code(depths.dtype), cum.data_ptr(),
-                                         v, w_pad, h_pad, tile_size, config.alpha_threshold, row_begin, row_end,
-                                         int(use_depth16), near, far, keys.data_ptr(), values.data_ptr(), stream),
-                 "map_to_tiles")
-      keys_sorted, overlap_to_point = sort_pairs(keys, values, 8, 32, 32 + tile_bits)
-      _lib.check(lib.ms_find_ranges(keys_sorted.data_ptr(), total, 8, 32, num_tiles, tile_ranges.data_ptr(), stream),
-                 "map_to_tiles")
-      _lib.check(lib.ms_tile_depth_sort(tile_ranges.data_ptr(), num_tiles, keys_sorted.data_ptr(),
-                                        overlap_to_point.data_ptr(), keys.data_ptr(), stream), "map_to_tiles")
+      # 2. the frame executor's direct sequence at the exact capacity K: tile ids and payload words depth key << 32 |
+      #    point (ndc / 16 bit quantisation fused) in storage order, STABLE sort on the ids, ranges, each run sorted by
+      #    its payload words by one workgroup (csrc/tile_sort.hip)
+      overlap_to_point = torch.empty((total,), dtype=torch.int32, device=device)
+      counters = torch.empty((8,), dtype=torch.int32, device=device)
+      args = (points.data_ptr(), depths.data_ptr(), _lib.dtype_code(depths.dtype), cum.data_ptr(), v, w_pad, h_pad, tile_size,
+              config.alpha_threshold, row_begin, row_end, int(use_depth16), near, far, total, overlap_to_point.data_ptr(),
+              tile_ranges.data_ptr(), counters.data_ptr())
+      nb = ctypes.c_size_t(0)
+      _lib.check(lib.ms_map_tiles_direct(*args, None, ctypes.byref(nb), stream), "map_to_tiles")
+      tmp = scratch(nb.value)
+      _lib.check(lib.ms_map_tiles_direct(*args, tmp.data_ptr(), ctypes.byref(nb), stream), "map_to_tiles")
       return overlap_to_point, tile_ranges
 
     assert method == 'presort', f"map_to_tiles: unknown method {method!r}"

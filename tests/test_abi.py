@@ -28,11 +28,11 @@ def test_every_declared_symbol_is_exported(lib):
 
 
 def test_version_and_error_string(lib):
-  assert lib.ms_version() == 500     # MS_VERSION of include/mi355_splat.h (0.5.0: sized structs, run-time split parameters)
+  assert lib.ms_version() == 501     # MS_VERSION of include/mi355_splat.h (0.5.x: sized structs, run-time split parameters; 501: one direct mapper)
   assert lib.ms_version() == _lib.ABI_VERSION
-  assert re.search(r'#define MS_VERSION (\d+)', HEADER.read_text()).group(1) == '500'
+  assert re.search(r'#define MS_VERSION (\d+)', HEADER.read_text()).group(1) == '501'
   import taichi_splatting_amd
-  assert taichi_splatting_amd.__version__ == '0.5.0'
+  assert taichi_splatting_amd.__version__ == '0.5.1'
   assert isinstance(lib.ms_last_error_string(), bytes)
 
 
@@ -77,7 +77,7 @@ def test_struct_layouts_match_the_header(tmp_path):
             'ms_frame_grads': _lib.FrameGradsC}[cname]
       assert getattr(py, field).offset == want, (key, getattr(py, field).offset, want)
   d = _lib.FrameDescC(n=1)
-  assert d.struct_size == c['ms_frame_desc'] and d.abi_version == 500
+  assert d.struct_size == c['ms_frame_desc'] and d.abi_version == 501
   assert _lib.FrameInputsC().struct_size == c['ms_frame_inputs'] and _lib.FrameGradsC().struct_size == c['ms_frame_grads']
 
 

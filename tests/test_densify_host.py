@@ -28,9 +28,9 @@ def test_header_library_and_binding_agree(lib):
     assert hasattr(lib, name), f"{name} is not exported"
   assert set(_lib.SIGNATURES) == declared
   # additive only: the ABI generation is unchanged
-  assert lib.ms_version() == 500 == _lib.ABI_VERSION
+  assert lib.ms_version() == 501 == _lib.ABI_VERSION
   import taichi_splatting_amd
-  assert taichi_splatting_amd.__version__ == '0.5.0'
+  assert taichi_splatting_amd.__version__ == '0.5.1'
 
 
 def test_descriptor_layout_matches_the_header(tmp_path):

@@ -1,6 +1,6 @@
 """-m gpu: the variants of the integer primitives that exist only inside the frame executor — the adaptive depth pre-sort
-(``radix_sort_depth_adaptive``), the device-count sorts (``sort_pairs_u32_dev_launch`` / ``sort_pairs_u64_dev_launch``) and
-the range kernels ``find_ranges4_kernel`` / ``find_ranges2_u64_kernel`` of csrc/scan_sort.hip — driven through the C-ABI
+(``radix_sort_depth_adaptive``), the device-count sorts (``sort_pairs_u32_dev_launch`` / ``sort_ids_payload_dev_launch``) and
+the range kernels ``find_ranges4_kernel`` / ``find_ranges_ids_kernel`` of csrc/scan_sort.hip — driven through the C-ABI
 (``ms_frame_layout_query``, ``ms_frame_project_count``, ``ms_frame_map_raster``) with inputs that choose the route of the
 pre-sort and the overlap total K to the element.
 

@@ -1,14 +1,16 @@
 """-m gpu: the direct-order mapper on narrow tile ids with 8-byte (depth key, point) payloads (ms_map_tiles_direct: the
 launch sequence of the frame executor's direct branch, callable without a frame) against
 
-  * the numpy oracle (oracle/mapper.py: one lexsort by (tile, depth bits, point index)), and
-  * the sequence of the public primitives ms_tile_emit_keys64 -> ms_radix_sort_pairs -> ms_find_ranges ->
-    ms_tile_depth_sort (map_to_tiles_strip(method='direct')), which still runs on u64 keys with int32 values.
+  * the numpy oracle (oracle/mapper.py: one lexsort by (tile, depth bits, point index)),
+  * map_to_tiles_strip(method='presort'), the second construction of the same lists on the device (gaussians sorted by
+    depth, overlaps sorted by tile id: no kernel of the direct sequence behind its order), and
+  * map_to_tiles_strip(method='direct'), the operator's wrapper of the same entry point: capacity exactly K, its own
+    allocations and early returns.
 
-Integer lists: overlap_to_point and tile_ranges must be IDENTICAL, no tolerance.  The scenes aim at what the narrow form
-changed: the 2-byte / 4-byte id switch at 65 536 tiles, the radix block edge (4096 pairs), runs at the class boundaries
-of tile_sort.hip (1024 / 2560 / 5120) now read as payload words only — a run of ONE entry must still be copied out —
-the declined (bounded) path, ties, capacity above and below K, strips, and a float64 frame.  The mapper runs without an
+Integer lists: overlap_to_point and tile_ranges must be IDENTICAL, no tolerance.  The scenes aim at the edges of the
+narrow form: the 2-byte / 4-byte id switch at 65 536 tiles, the radix block edge (4096 pairs), runs at the class
+boundaries of tile_sort.hip (1024 / 2560 / 5120) read as payload words only — a run of ONE entry must still be copied
+out — the declined (bounded) path, ties, capacity above and below K, strips, and a float64 frame.  The mapper runs without an
 image, so the 4096 x 4096 cases cost what their few thousand gaussians cost."""
 import ctypes
 
@@ -67,7 +69,8 @@ def direct(p, depth, size, tile=16, depth16=False, rows=None, ndc=None, capacity
 
 
 def check(p, depth, size, tile=16, depth16=False, rows=None, **kw):
-  """the entry point == the oracle == the primitives' sequence; returns (K, tile_ranges of the oracle)"""
+  """the entry point == the oracle == the pre-sort construction == the operator's wrapper; returns (K, tile_ranges of
+  the oracle)"""
   p, depth = p.to(torch.float32), depth.reshape(-1, 1)
   o2p, ranges, counters, k = direct(p, depth, size, tile, depth16, rows, **kw)
   want_o2p, want_ranges, _ = omap.map_to_tiles(p.numpy(), depth.to(torch.float32).numpy(), size, tile, THR, use_depth16=depth16,
@@ -79,8 +82,9 @@ def check(p, depth, size, tile=16, depth16=False, rows=None, **kw):
   assert bad.size == 0, f"{bad.size} of {k} entries differ from the oracle, first at {int(bad[0])}"
   assert bool((o2p[k:] == UNTOUCHED).all())                       # nothing written past K
   cfg = RasterConfig(tile_size=tile, pixel_stride=(1, 1) if tile == 8 else (2, 2), alpha_threshold=THR)
-  m_o2p, m_ranges = map_to_tiles_strip(p.to(DEV), depth.to(DEV), size, cfg, use_depth16=depth16, tile_rows=rows, method='direct')
-  assert torch.equal(m_ranges, ranges) and torch.equal(m_o2p, o2p[:k])
+  for method in ('presort', 'direct'):
+    m_o2p, m_ranges = map_to_tiles_strip(p.to(DEV), depth.to(DEV), size, cfg, use_depth16=depth16, tile_rows=rows, method=method)
+    assert torch.equal(m_ranges, ranges) and torch.equal(m_o2p, o2p[:k]), method
   return k, want_ranges
 
 
@@ -216,14 +220,16 @@ def test_a_strip_of_tile_rows():
 def test_float64_depths_and_ndc_keys():
   p, depth = random_scene(4000, (200, 144), 2.0, 12)
   check(p, depth.double(), (200, 144))
-  # ndc keys are made inside the emit kernel from camera depths: against the primitives' sequence, which makes them
-  # with the same function (the oracle takes ready keys)
+  # ndc keys are made inside the emit kernel from camera depths: against the pre-sort construction, whose first radix
+  # pass makes them with the same function, depth_sort_key (the oracle takes ready keys)
   cam_depth = (0.2 + 50.0 * depth).double()
   cfg = RasterConfig(tile_size=16, alpha_threshold=THR)
   o2p, ranges, counters, k = direct(p, cam_depth, (200, 144), ndc=(0.1, 100.0))
-  m_o2p, m_ranges = map_to_tiles_strip(p.to(DEV), cam_depth.reshape(-1, 1).to(DEV), (200, 144), cfg, ndc_range=(0.1, 100.0),
-                                       method='direct')
-  assert counters[:3] == [k, k, 0] and torch.equal(m_ranges, ranges) and torch.equal(m_o2p, o2p[:k])
+  assert counters[:3] == [k, k, 0]
+  for method in ('presort', 'direct'):                            # 'direct': the wrapper hands ndc_range on
+    m_o2p, m_ranges = map_to_tiles_strip(p.to(DEV), cam_depth.reshape(-1, 1).to(DEV), (200, 144), cfg, ndc_range=(0.1, 100.0),
+                                         method=method)
+    assert torch.equal(m_ranges, ranges) and torch.equal(m_o2p, o2p[:k]), method
 
 
 def test_a_float64_frame_on_the_direct_sequence():

@@ -139,10 +139,11 @@ def test_render_path_with_culled_rows_and_ndc_keys(use_depth16):
   assert torch.equal(o2p, pts.idx.reshape(-1).to(torch.int32)[want_o2p.long()])
 
 
-# ---- the primitive through the C-ABI (ms_tile_depth_sort) against a stable composite sort in torch -------------------
+# ---- the primitive through the C-ABI (ms_tile_payload_sort) against a stable composite sort in torch -----------------
+UNTOUCHED = -7
+
 
 def run_primitive(lengths, keys):
-  import ctypes
   from taichi_splatting_amd import _lib
   lib = _lib.load()
   lengths = torch.as_tensor(lengths, dtype=torch.int64)
@@ -155,11 +156,13 @@ def run_primitive(lengths, keys):
   ids = torch.arange(k, dtype=torch.int32) * 3 + 1                 # ascending inside every run, not the position
   composite = (tile << 32) | keys
   want = ids[torch.sort(composite, stable=True).indices]
-  srt = composite.to(DEV)
-  o2p = ids.to(DEV)
+  payload = ((keys << 32) | ids.to(torch.int64)).to(DEV)
+  # output only: every entry must be written, the runs of one entry and of one key included
+  o2p = torch.full((k,), UNTOUCHED, dtype=torch.int32, device=DEV)
   scratch = torch.empty(k, dtype=torch.int64, device=DEV)
-  _lib.check(lib.ms_tile_depth_sort(ranges.to(DEV).data_ptr(), lengths.numel(), srt.data_ptr(), o2p.data_ptr(),
-                                    scratch.data_ptr(), _lib.current_stream(torch.device(DEV))), "ms_tile_depth_sort")
+  ranges = ranges.to(DEV)
+  _lib.check(lib.ms_tile_payload_sort(ranges.data_ptr(), lengths.numel(), payload.data_ptr(), o2p.data_ptr(),
+                                      scratch.data_ptr(), _lib.current_stream(torch.device(DEV))), "ms_tile_payload_sort")
   torch.cuda.synchronize()
   bad = (o2p.cpu() != want).nonzero()
   assert bad.numel() == 0, f"{bad.numel()} of {k} entries differ, first at {int(bad[0])} (tile {int(tile[bad[0]])})"

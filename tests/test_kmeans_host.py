@@ -303,4 +303,4 @@ def test_names_are_public_and_installed():
   import importlib
   assert importlib.import_module('taichi_splatting.misc.kmeans') is km
   assert importlib.import_module('taichi_splatting.scene_codec').CompressedScene is CompressedScene
-  assert tsa.__version__ == '0.5.0'
+  assert tsa.__version__ == '0.5.1'

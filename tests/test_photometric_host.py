@@ -125,7 +125,7 @@ def test_float32_composition_is_inside_the_tolerance(kind):
 def test_abi_declares_and_checks_the_photometric_entry_points(lib):
   from tests.test_abi import declared_functions
   assert {'ms_photometric_fwd', 'ms_photometric_bwd'} <= set(declared_functions())
-  assert re.search(r'#define MS_VERSION (\d+)', (_lib.CSRC_DIR.parent.parent / 'include' / 'mi355_splat.h').read_text()).group(1) == '500'
+  assert re.search(r'#define MS_VERSION (\d+)', (_lib.CSRC_DIR.parent.parent / 'include' / 'mi355_splat.h').read_text()).group(1) == '501'
   n = ctypes.c_size_t(0)
 
   def fwd(h=64, w=64, c=3, dtype=_lib.MS_F32, pad=_lib.PAD_SAME, lam=0.2, image=None, tmp=None, out=None, tmp_bytes=n):

@@ -24,7 +24,7 @@ def test_header_declares_the_active_degree_abi():
   fields = re.findall(r'^\s*(?:u?int\d+_t|double|ms_raster_config)\s+([^;]+);', desc, re.M)
   names = [n.strip() for f in fields for n in f.split(',')]
   assert names[names.index('split_seg_len') + 1] == 'sh_active_bands', names      # behind split_seg_len
-  assert re.search(r'#define MS_VERSION 500\b', HEADER)
+  assert re.search(r'#define MS_VERSION 501\b', HEADER)
 
 
 def test_zeroed_descriptor_means_all_bands():

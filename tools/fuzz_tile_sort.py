@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Randomised cross-check of ms_tile_depth_sort (csrc/tile_sort.hip) against a stable composite sort in torch.
+"""Randomised cross-check of ms_tile_payload_sort (csrc/tile_sort.hip: the per-tile sort of the direct-order mapper, on
+payload words key << 32 | index) against a stable composite sort in torch.
 
 Every round draws a set of tile runs (lengths from a mixture that reaches every size class, the cost fallback and the
 global radix path) and 32 bit keys from a mixture of shapes (uniform bits, uniform floats, binade spreads, clusters with
@@ -86,10 +87,12 @@ def main():
     ids = torch.arange(k, dtype=torch.int32)
     composite = (tile << 32) | keys
     want = ids[torch.sort(composite, stable=True).indices]
-    srt, o2p = composite.to(DEV), ids.to(DEV)
+    payload = ((keys << 32) | ids.to(torch.int64)).to(DEV)
+    o2p = torch.full((k,), -1, dtype=torch.int32, device=DEV)      # output only: every entry of a run must be written
     scratch = torch.empty(k, dtype=torch.int64, device=DEV)
-    _lib.check(lib.ms_tile_depth_sort(ranges.to(DEV).data_ptr(), lengths.numel(), srt.data_ptr(), o2p.data_ptr(),
-                                      scratch.data_ptr(), stream), "ms_tile_depth_sort")
+    ranges = ranges.to(DEV)
+    _lib.check(lib.ms_tile_payload_sort(ranges.data_ptr(), lengths.numel(), payload.data_ptr(), o2p.data_ptr(),
+                                        scratch.data_ptr(), stream), "ms_tile_payload_sort")
     torch.cuda.synchronize()
     bad = (o2p.cpu() != want).nonzero()
     if bad.numel():
