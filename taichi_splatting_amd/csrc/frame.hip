@@ -450,9 +450,15 @@ extern "C" int ms_frame_map_raster(const ms_frame_desc* desc, const ms_frame_inp
   if (cut) split = split_scratch_carve(kk + L.split_scratch, d.k_capacity, d.raster.tile_size, frame_split_params(desc));
   // the colours of a projected-input frame may still be arriving (a rank step's second forward collective)
   if (in->colours_ready_event) MS_CHECK_HIP(hipStreamWaitEvent(s, (hipEvent_t)in->colours_ready_event, 0));
-  return raster_fwd_launch(points7, colours, frame_uses_rows(desc) ? (const float*)(kn + L.splat_rows) : nullptr, ranges, o2p,
-                           d.image_w, d.image_h, d.f, &d.raster, out_image, out_alpha, out_visibility, g.row_begin, g.row_end,
-                           d.dtype, stream, cut ? &split : nullptr, in->longest_run_host);
+  RasterArgs a{};
+  a.dtype = d.dtype; a.f = d.f; a.points7 = points7; a.features = colours;
+  a.splat_rows = frame_uses_rows(desc) ? (const float*)(kn + L.splat_rows) : nullptr;
+  a.tile_ranges = ranges; a.overlap_to_point = o2p;
+  a.image_w = d.image_w; a.image_h = d.image_h; a.cfg = &d.raster; a.tile_row_begin = g.row_begin; a.tile_row_end = g.row_end;
+  a.split = cut ? &split : nullptr;
+  a.out_image = out_image; a.out_alpha = out_alpha; a.out_visibility = out_visibility;
+  a.long_run_word = in->longest_run_host;
+  return raster_fwd_launch(a, s, __func__);
 }
 
 extern "C" int ms_map_tiles_direct(const float* points7, const void* depth, int depth_dtype, const int32_t* cum, int64_t v,
@@ -541,6 +547,14 @@ extern "C" int ms_frame_backward(const ms_frame_desc* desc, const ms_frame_input
     MS_CHECK_ARG(gr->boundary_stride >= 7 + d.f && d.dtype == MS_F32, "boundary_stride: rows of >= 7 + f floats, float32 frames");
     MS_CHECK_ARG(given || (moments && raster_only), "boundary_stride: MS_BACKWARD_GAUSSIANS, or MS_BACKWARD_RASTER on the moments path");
   }
+  // the raster backward of this frame, whichever kernel family serves it
+  RasterArgs r{};
+  r.dtype = d.dtype; r.f = d.f; r.points7 = points7; r.features = colours;
+  r.tile_ranges = ranges; r.overlap_to_point = o2p;
+  r.image_w = d.image_w; r.image_h = d.image_h; r.cfg = &d.raster; r.tile_row_begin = g.row_begin; r.tile_row_end = g.row_end;
+  r.image = gr->image; r.grad_image = gr->grad_image;
+  r.grad_points7 = gr->grad_points7; r.grad_features = gr->grad_colours;
+  r.point_heuristic = d.raster.compute_point_heuristic ? gr->point_heuristic : nullptr;
   if (given) {
     MS_CHECK_ARG(!d.projected_input, "projected input has no per-gaussian backward");
     if (gr->gather_world > 0)
@@ -554,21 +568,16 @@ extern "C" int ms_frame_backward(const ms_frame_desc* desc, const ms_frame_input
     SplitScratch split{};
     const bool cut = frame_uses_split(desc) && keep_k != nullptr;
     if (cut) split = split_scratch_carve(kk + L.split_scratch, d.k_capacity, d.raster.tile_size, frame_split_params(desc));
-    MS_TRY(raster_bwd_moments_launch(points7, colours, ranges, o2p, gr->image, gr->grad_image, d.image_w, d.image_h, &d.raster,
-                                     (float*)gr->moments, gr->deterministic, gr->fixed_exp, g.row_begin, g.row_end,
-                                     gr->grad_image_broadcast, s,
-                                     frame_uses_rows(desc) ? (const float*)(kn + L.splat_rows) : nullptr,
-                                     cut ? &split : nullptr));
+    r.splat_rows = frame_uses_rows(desc) ? (const float*)(kn + L.splat_rows) : nullptr;
+    r.split = cut ? &split : nullptr;
+    r.grad_broadcast = gr->grad_image_broadcast;
+    r.moments = (float*)gr->moments; r.deterministic = gr->deterministic; r.fixed_exp = gr->fixed_exp;
+    MS_TRY(raster_bwd_moments_launch(r, s, __func__));
     if (raster_only)
-      return moments_finalize_rezero_launch((const float*)points7, (float*)gr->moments, gr->deterministic, gr->fixed_exp,
-                                            d.n, (float*)gr->grad_points7, (float*)gr->grad_colours,
-                                            d.raster.compute_point_heuristic ? (float*)gr->point_heuristic : nullptr, s,
-                                            gr->boundary_stride, d.projected_input && gr->stage != MS_BACKWARD_RASTER ? 0 : gr->boundary_form);
+      return moments_finalize_launch(r, d.n, MomentsFinalizeForm{gr->boundary_stride, d.projected_input && gr->stage != MS_BACKWARD_RASTER ? 0 : gr->boundary_form, true}, s);
   } else {
     MS_CHECK_ARG(gr->grad_points7 || gr->grad_colours, "no gradient accumulator");
-    MS_TRY(ms_raster_bwd(points7, colours, ranges, o2p, gr->image, gr->grad_image, d.image_w, d.image_h, d.f, &d.raster,
-                         gr->grad_points7, gr->grad_colours, d.raster.compute_point_heuristic ? gr->point_heuristic : nullptr,
-                         g.row_begin, g.row_end, d.dtype, stream));
+    MS_TRY(raster_bwd_launch(r, s, __func__));
     if (raster_only) return 0;
   }
 

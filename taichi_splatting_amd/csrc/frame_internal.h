@@ -129,24 +129,63 @@ int sh_fwd_inplace_launch(const void* params, const void* positions, const void*
 // executor's projection and SH kernels fill for the product raster kernels, which then gather one 128-byte line per
 // splat.  The dense arrays stay what every other consumer (mapper, per-gaussian backward, outputs) reads.
 bool raster_uses_splat_rows(const ms_raster_config* cfg, int f, int dtype);
-// ms_raster_fwd; splat_rows != NULL: the product kernels read the table instead of points7 / features
-int raster_fwd_launch(const void* points7, const void* features, const float* splat_rows, const int32_t* tile_ranges,
-                      const int32_t* overlap_to_point, int image_w, int image_h, int f, const ms_raster_config* cfg,
-                      void* out_image, void* out_alpha, void* out_visibility, int tile_row_begin, int tile_row_end,
-                      int dtype, void* stream, const struct SplitScratch* split = nullptr, int32_t* long_run_word = nullptr);
+
+// Everything one raster launch reads or writes: the C entry points and the frame executor fill one record per pass and
+// hand it to one launcher.  Fields a pass does not use stay zero.
+struct RasterArgs {
+  int dtype;                 // MS_F32 / MS_F64
+  int f;                     // feature channels per splat
+  const void *points7, *features;   // (n, 7) packed 2D gaussians, (n, f) features
+  const float* splat_rows;   // NULL: the dense arrays above; else the table the product kernels gather from instead
+  const int32_t *tile_ranges, *overlap_to_point;
+  int image_w, image_h;
+  const ms_raster_config* cfg;
+  int tile_row_begin, tile_row_end;   // window of tile rows as the caller gave it (raster_window clamps it to the image)
+  const struct SplitScratch* split;   // plan and states of the segments of long tile runs (raster_common.h); NULL: no segments
+  // forward
+  void *out_image, *out_alpha, *out_visibility;
+  int32_t* long_run_word;    // pinned host word (may be NULL): the length of a run above the split threshold is noted there
+  // backward inputs
+  const void *image, *grad_image;
+  int grad_broadcast;        // grad_image is ONE pixel's f values (ms_frame_grads.grad_image_broadcast): moments backward only
+  // moments backward (raster_bwd_scan.hip: float32 RGB, plain pdf)
+  float* moments;            // (n, MS_MOMENT_ROW) float, int64 when deterministic
+  int deterministic;
+  const int32_t* fixed_exp;  // deterministic: binary exponents of the fixed-point scales
+  // generic backward outputs (each may be NULL)
+  void *grad_points7, *grad_features, *point_heuristic;
+};
+constexpr int RASTER_MAX_F = 4;          // forward, and backward without point heuristics: wider features are chunked on the host
+constexpr int RASTER_MAX_F_HEUR = 16;    // backward WITH point heuristics: F = 8 and 16 are instantiated too (raster_bwd_launch)
+// the tiles of a launch: the record's row window clamped to the image
+struct RasterWindow {
+  int tiles_wide, tile_begin, num_tiles;   // tile_begin = first tile id of the window
+  bool empty;                              // no tile row left: the caller returns 0 before any launch
+};
+// The one validator of the raster stage: cfg, image size, dtype, tile size and feature count (1..4, or 8 / 16 where
+// max_f admits them), in this order.  `who` names the entry point in the messages.
+int raster_window(const RasterArgs& a, const char* who, int max_f, RasterWindow* w);
+// ms_raster_fwd (also _rows, _split and the frame executor's forward)
+int raster_fwd_launch(const RasterArgs& a, hipStream_t s, const char* who);
+// ms_raster_bwd: atomic gradient commits, every dtype / feature count / pdf
+int raster_bwd_launch(const RasterArgs& a, hipStream_t s, const char* who);
+
+// ---- raster_fast.hip --------------------------------------------------------------------------------------------
+// the product kernels (float32 RGB, plain pdf, blending) behind the two launchers above
+void raster_fwd_f32x3_launch(const RasterArgs& a, const RasterWindow& w, hipStream_t s);
+void raster_bwd_f32x3_launch(const RasterArgs& a, const RasterWindow& w, hipStream_t s);
 
 // ---- raster_bwd_scan.hip ----------------------------------------------------------------------------------------
-// ms_raster_bwd_moments with grad_broadcast: dL/dimage given as ONE pixel's f values (ms_frame_grads.grad_image_broadcast)
-int raster_bwd_moments_launch(const void* points7, const void* features, const int32_t* tile_ranges,
-                              const int32_t* overlap_to_point, const void* image, const void* grad_image, int image_w,
-                              int image_h, const ms_raster_config* cfg, float* moments, int deterministic,
-                              const int32_t* fixed_exp, int tile_row_begin, int tile_row_end, int grad_broadcast,
-                              hipStream_t s, const float* splat_rows = nullptr, const struct SplitScratch* split = nullptr);
-// ms_raster_moments_finalize that also clears the rows it reads (persistent moments buffer)
-// row_stride > 0: grad_points7 / grad_features are columns of one row-major array with that many floats per row
-int moments_finalize_rezero_launch(const float* points7, float* moments, int deterministic, const int32_t* fixed_exp,
-                                   int64_t n, float* grad_points7, float* grad_features, float* point_heuristic,
-                                   hipStream_t s, int row_stride = 0, int covariance_form = 0);
+// ms_raster_bwd_moments (also _rows, _split and the frame executor's backward)
+int raster_bwd_moments_launch(const RasterArgs& a, hipStream_t s, const char* who);
+// ms_raster_moments_finalize: the moment rows of n gaussians (points7, moments, deterministic, fixed_exp of the record)
+// -> grad_points7 / grad_features / point_heuristic of the record (float32, each may be NULL)
+struct MomentsFinalizeForm {
+  int row_stride;        // > 0: grad_points7 / grad_features are columns of one row-major array with that many floats per row
+  int covariance_form;   // MS_BOUNDARY_COVARIANCE rows
+  bool rezero;           // also clear the rows it reads (the frame executor's persistent moments buffer)
+};
+int moments_finalize_launch(const RasterArgs& a, int64_t n, const MomentsFinalizeForm& form, hipStream_t s);
 
 // ---- gaussian_bwd.hip -------------------------------------------------------------------------------------------
 // One pass over the gaussians for the whole per-gaussian backward of a frame: 2D-boundary gradients (from the raster

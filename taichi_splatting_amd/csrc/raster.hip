@@ -1,9 +1,11 @@
 // raster.hip — tile-based alpha compositing of sorted 2D gaussians: generic forward / backward
 // templates (float and double, F = 1..4 channels, tile 8/16/32, plain or antialiased pdf, blending or
-// quantile render, visibility, point heuristics) and the C-ABI dispatch.  The product path (float, RGB,
-// plain pdf, blending) is dispatched to the hand-tuned kernels of raster_fast.hip; everything else —
-// in particular the float64 instantiations the reference-style gradcheck tests run — uses the
-// templates below.
+// quantile render, visibility, point heuristics) and the host side of the raster stage: every C entry point and the
+// frame executor fill one RasterArgs record (frame_internal.h), raster_window validates it and clamps the row window,
+// and raster_fwd_launch / raster_bwd_launch turn its run-time dtype, channel count, tile size and switches into
+// template arguments (with_constant, raster_common.h), each kernel's argument list written once.  The product path
+// (float, RGB, plain pdf, blending) goes to the hand-tuned kernels of raster_fast.hip; everything else — in
+// particular the float64 instantiations the reference-style gradcheck tests run — uses the templates below.
 //
 // Work decomposition (gfx950, wave64), shared with raster_fast.hip:
 //   * one workgroup per screen tile (tile_size^2 threads), one wavefront per 8x8 pixel patch,
@@ -28,8 +30,6 @@
 
 namespace ms {
 
-constexpr int RASTER_MAX_F = 4;          // forward, and backward without point heuristics: wider features are chunked on the host
-constexpr int RASTER_MAX_F_HEUR = 16;    // backward WITH point heuristics: F = 8 and 16 are instantiated too (see ms_raster_bwd)
 // number of per-pixel gradient values a backward pass reduces per splat, padded to the butterfly's 16 slots
 template <int F> struct GradSlots { static constexpr int N = F <= 4 ? 16 : 7 + F + 2; };
 
@@ -478,130 +478,125 @@ raster_bwd_kernel(const T* __restrict__ points, const T* __restrict__ feats,
 }
 
 // ------------------------------------------------------------------------------------------------
-// dispatch
+// dispatch: one record (RasterArgs, frame_internal.h), one validator, one launcher per pass
 // ------------------------------------------------------------------------------------------------
 template <typename T>
-static RasterParams<T> make_raster_params(int w, int h, const ms_raster_config* cfg, int row_begin) {
+static RasterParams<T> make_raster_params(const RasterArgs& a, const RasterWindow& w) {
   RasterParams<T> rp;
-  rp.width = w; rp.height = h;
-  rp.tiles_wide = (w + cfg->tile_size - 1) / cfg->tile_size;
-  rp.tile_begin = row_begin * rp.tiles_wide;
-  rp.clamp_max_alpha = (T)cfg->clamp_max_alpha;
-  rp.alpha_threshold = (T)cfg->alpha_threshold;
-  rp.saturate_threshold = (T)cfg->saturate_threshold;
+  rp.width = a.image_w; rp.height = a.image_h;
+  rp.tiles_wide = w.tiles_wide; rp.tile_begin = w.tile_begin;
+  rp.clamp_max_alpha = (T)a.cfg->clamp_max_alpha;
+  rp.alpha_threshold = (T)a.cfg->alpha_threshold;
+  rp.saturate_threshold = (T)a.cfg->saturate_threshold;
   return rp;
 }
 
-template <typename T, int F, int TS>
-static void launch_fwd(const void* points, const void* feats, const int32_t* ranges, const int32_t* o2p,
-                       int w, int h, const ms_raster_config* cfg, void* image, void* alpha, void* vis,
-                       int row_begin, int num_tiles, hipStream_t s) {
-  const RasterParams<T> rp = make_raster_params<T>(w, h, cfg, row_begin);
-  const dim3 grid((unsigned)num_tiles), block(TS * TS);
-#define MS_FWD(AA, BLEND, VIS)                                                                        \
-  raster_fwd_kernel<T, F, TS, AA, BLEND, VIS><<<grid, block, 0, s>>>(                                 \
-      (const T*)points, (const T*)feats, ranges, o2p, rp, (T*)image, (T*)alpha, (T*)vis)
-  const bool aa = cfg->antialias, blend = cfg->use_alpha_blending, visf = cfg->compute_visibility && vis;
-  if (!blend) {
-    if (aa) { if (visf) MS_FWD(true, false, true); else MS_FWD(true, false, false); }
-    else { if (visf) MS_FWD(false, false, true); else MS_FWD(false, false, false); }
-  }
-  else if (aa) { if (visf) MS_FWD(true, true, true); else MS_FWD(true, true, false); }
-  else { if (visf) MS_FWD(false, true, true); else MS_FWD(false, true, false); }
-#undef MS_FWD
-}
-
-template <typename T, int F, int TS>
-static void launch_bwd(const void* points, const void* feats, const int32_t* ranges, const int32_t* o2p,
-                       const void* image, const void* grad_image, int w, int h, const ms_raster_config* cfg,
-                       void* gp, void* gf, void* heur, int row_begin, int num_tiles, hipStream_t s) {
-  const RasterParams<T> rp = make_raster_params<T>(w, h, cfg, row_begin);
-  const dim3 grid((unsigned)num_tiles), block(TS * TS);
-#define MS_BWD(AA, HEUR)                                                                           \
-  raster_bwd_kernel<T, F, TS, AA, HEUR><<<grid, block, 0, s>>>(                                    \
-      (const T*)points, (const T*)feats, ranges, o2p, (const T*)image, (const T*)grad_image, rp,   \
-      (T*)gp, (T*)gf, (T*)heur)
-  const bool aa = cfg->antialias, hf = cfg->compute_point_heuristic && heur;
-  if (aa) { if (hf) MS_BWD(true, true); else MS_BWD(true, false); }
-  else { if (hf) MS_BWD(false, true); else MS_BWD(false, false); }
-#undef MS_BWD
-}
-
-template <typename T, int F, typename... Args>
-static int dispatch_ts_fwd(int ts, Args... args) {
-  switch (ts) {
-    case 8: launch_fwd<T, F, 8>(args...); return 0;
-    case 16: launch_fwd<T, F, 16>(args...); return 0;
-    case 32: launch_fwd<T, F, 32>(args...); return 0;
-  }
-  return MS_ERR_UNSUPPORTED;
-}
-
-// F = 8 / 16: backward with point heuristics only (prune_cost and split_score are not linear in the channels, so
-// they cannot be assembled from 4-channel chunks: backward.py:171-194 forms alpha_grad over ALL channels first)
-template <typename T, int F, int TS>
-static void launch_bwd_wide(const void* points, const void* feats, const int32_t* ranges, const int32_t* o2p,
-                            const void* image, const void* grad_image, int w, int h, const ms_raster_config* cfg,
-                            void* gp, void* gf, void* heur, int row_begin, int num_tiles, hipStream_t s) {
-  const RasterParams<T> rp = make_raster_params<T>(w, h, cfg, row_begin);
-  const dim3 grid((unsigned)num_tiles), block(TS * TS);
-  if (cfg->antialias)
-    raster_bwd_kernel<T, F, TS, true, true><<<grid, block, 0, s>>>((const T*)points, (const T*)feats, ranges, o2p, (const T*)image,
-                                                                   (const T*)grad_image, rp, (T*)gp, (T*)gf, (T*)heur);
-  else
-    raster_bwd_kernel<T, F, TS, false, true><<<grid, block, 0, s>>>((const T*)points, (const T*)feats, ranges, o2p, (const T*)image,
-                                                                    (const T*)grad_image, rp, (T*)gp, (T*)gf, (T*)heur);
-}
-
-template <typename T, int F, typename... Args>
-static int dispatch_ts_bwd_wide(int ts, Args... args) {
-  switch (ts) {
-    case 8: launch_bwd_wide<T, F, 8>(args...); return 0;
-    case 16: launch_bwd_wide<T, F, 16>(args...); return 0;
-    case 32: launch_bwd_wide<T, F, 32>(args...); return 0;
-  }
-  return MS_ERR_UNSUPPORTED;
-}
-
-template <typename T, int F, typename... Args>
-static int dispatch_ts_bwd(int ts, Args... args) {
-  switch (ts) {
-    case 8: launch_bwd<T, F, 8>(args...); return 0;
-    case 16: launch_bwd<T, F, 16>(args...); return 0;
-    case 32: launch_bwd<T, F, 32>(args...); return 0;
-  }
-  return MS_ERR_UNSUPPORTED;
-}
+// dtype -> type, like with_constant (raster_common.h): fn(float{}) / fn(double{})
+template <typename Fn>
+static void with_dtype(int dtype, Fn&& fn) { if (dtype == MS_F32) fn(float{}); else fn(double{}); }
 
 }  // namespace ms
 
 using namespace ms;
 
-// product-path kernels (float, F = 3, plain pdf, blending): raster_fast.hip
-bool ms_raster_fwd_fast(const void* points, const void* feats, const int32_t* ranges, const int32_t* o2p,
-                        int w, int h, const ms_raster_config* cfg, void* image, void* alpha, void* visibility,
-                        int row_begin, int num_tiles, hipStream_t s, const float* splat_rows, const SplitScratch* split,
-                        int32_t* long_run_word);
-bool ms_raster_bwd_fast(const void* points, const void* feats, const int32_t* ranges, const int32_t* o2p,
-                        const void* image, const void* grad_image, int w, int h, const ms_raster_config* cfg,
-                        void* gp, void* gf, void* heur, int row_begin, int num_tiles, hipStream_t s);
-
-static int check_raster_common(const ms_raster_config* cfg, int w, int h, int f, int dtype, int* row_begin,
-                               int* row_end, const char* fn, int max_f = RASTER_MAX_F) {
-  if (!cfg) { set_error("%s: cfg is null", fn); return MS_ERR_BAD_ARG; }
-  if (w <= 0 || h <= 0) { set_error("%s: bad image size %dx%d", fn, w, h); return MS_ERR_BAD_ARG; }
-  if (dtype != MS_F32 && dtype != MS_F64) { set_error("%s: dtype must be MS_F32 or MS_F64", fn); return MS_ERR_BAD_ARG; }
-  if (cfg->tile_size != 8 && cfg->tile_size != 16 && cfg->tile_size != 32) {
-    set_error("%s: tile_size must be 8, 16 or 32 (got %d)", fn, cfg->tile_size); return MS_ERR_UNSUPPORTED;
-  }
-  if (f < 1 || f > max_f || (f > RASTER_MAX_F && f != 8 && f != 16)) {
+int ms::raster_window(const RasterArgs& a, const char* who, int max_f, RasterWindow* w) {
+  const ms_raster_config* cfg = a.cfg;
+  if (!cfg) { set_error("%s: cfg is null", who); return MS_ERR_BAD_ARG; }
+  if (a.image_w <= 0 || a.image_h <= 0) { set_error("%s: bad image size %dx%d", who, a.image_w, a.image_h); return MS_ERR_BAD_ARG; }
+  if (a.dtype != MS_F32 && a.dtype != MS_F64) { set_error("%s: dtype must be MS_F32 or MS_F64 (got %d)", who, a.dtype); return MS_ERR_BAD_ARG; }
+  const int ts = cfg->tile_size;
+  if (ts != 8 && ts != 16 && ts != 32) { set_error("%s: tile_size must be 8, 16 or 32 (got %d)", who, ts); return MS_ERR_UNSUPPORTED; }
+  if (a.f < 1 || a.f > max_f || (a.f > RASTER_MAX_F && a.f != 8 && a.f != 16)) {
     set_error("%s: feature size %d not supported: 1..%d, or 8 / 16 for the backward pass with point heuristics "
-              "(split or zero-pad the channels on the host)", fn, f, RASTER_MAX_F);
+              "(split or zero-pad the channels on the host)", who, a.f, RASTER_MAX_F);
     return MS_ERR_UNSUPPORTED;
   }
-  const int tiles_high = (h + cfg->tile_size - 1) / cfg->tile_size;
-  if (*row_begin < 0) *row_begin = 0;
-  if (*row_end > tiles_high) *row_end = tiles_high;
+  const int tiles_high = (a.image_h + ts - 1) / ts;
+  const int row_begin = a.tile_row_begin < 0 ? 0 : a.tile_row_begin;
+  const int row_end = a.tile_row_end > tiles_high ? tiles_high : a.tile_row_end;
+  w->tiles_wide = (a.image_w + ts - 1) / ts;
+  w->tile_begin = row_begin * w->tiles_wide;
+  w->empty = row_end <= row_begin;
+  w->num_tiles = w->empty ? 0 : (row_end - row_begin) * w->tiles_wide;
+  return 0;
+}
+
+bool ms::raster_uses_splat_rows(const ms_raster_config* cfg, int f, int dtype) {
+  return dtype == MS_F32 && f == 3 && !cfg->antialias && cfg->use_alpha_blending &&
+         (cfg->tile_size == 8 || cfg->tile_size == 16 || cfg->tile_size == 32);
+}
+
+// The product configuration (float, RGB, plain pdf, blending) goes to the kernels of raster_fast.hip, which gather
+// from the splat-row table when the record has one; everything else reads the dense arrays with the templates above.
+int ms::raster_fwd_launch(const RasterArgs& a, hipStream_t s, const char* who) {
+  RasterWindow w;
+  if (const int rc = raster_window(a, who, RASTER_MAX_F, &w)) return rc;
+  if (!a.tile_ranges || !a.out_image || !a.out_alpha) { set_error("%s: null pointer", who); return MS_ERR_BAD_ARG; }
+  if (w.empty) return 0;
+  const ms_raster_config* cfg = a.cfg;
+  if (a.dtype == MS_F32 && a.f == 3 && !cfg->antialias && cfg->use_alpha_blending) {
+    raster_fwd_f32x3_launch(a, w, s);
+  } else {
+    with_dtype(a.dtype, [&](auto t) { with_constant<1, 2, 3, 4>(a.f, [&](auto f) { with_tile_size(cfg->tile_size, [&](auto tile_size) {
+      using T = decltype(t);
+      constexpr int F = decltype(f)::value, TS = tile_size;
+      const RasterParams<T> rp = make_raster_params<T>(a, w);
+      auto launch = [&](auto AA, auto BLEND, auto VIS) {
+        raster_fwd_kernel<T, F, TS, AA, BLEND, VIS><<<dim3((unsigned)w.num_tiles), dim3(TS * TS), 0, s>>>(
+            (const T*)a.points7, (const T*)a.features, a.tile_ranges, a.overlap_to_point, rp, (T*)a.out_image,
+            (T*)a.out_alpha, (T*)a.out_visibility);
+      };
+      auto render = [&](auto BLEND) {
+        with_bool(cfg->antialias, [&](auto AA) {
+          with_bool(cfg->compute_visibility && a.out_visibility, [&](auto VIS) { launch(AA, BLEND, VIS); });
+        });
+      };
+      if (!cfg->use_alpha_blending) render(std::false_type{}); else render(std::true_type{});     // quantile render / blending
+    }); }); });
+  }
+  MS_CHECK_LAUNCH();
+  return 0;
+}
+
+// Atomic gradient commits.  Float RGB with the plain pdf goes to the patch backward of raster_fast.hip.
+// F = 8 / 16: with point heuristics only (prune_cost and split_score are not linear in the channels, so they cannot be
+// assembled from 4-channel chunks: backward.py:171-194 forms alpha_grad over ALL channels first)
+int ms::raster_bwd_launch(const RasterArgs& a, hipStream_t s, const char* who) {
+  const bool heur = a.cfg && a.cfg->compute_point_heuristic && a.point_heuristic;
+  RasterWindow w;
+  if (const int rc = raster_window(a, who, heur ? RASTER_MAX_F_HEUR : RASTER_MAX_F, &w)) return rc;
+  if (!a.tile_ranges || !a.image || !a.grad_image) { set_error("%s: null pointer", who); return MS_ERR_BAD_ARG; }
+  const ms_raster_config* cfg = a.cfg;
+  if (!cfg->use_alpha_blending) {
+    set_error("%s: backward requires use_alpha_blending (reference: tests/test_rasterizer.py:92-94)", who);
+    return MS_ERR_BAD_ARG;
+  }
+  if (w.empty) return 0;
+  if (!a.grad_points7 && !a.grad_features && !a.point_heuristic) return 0;
+  if (a.dtype == MS_F32 && a.f == 3 && !cfg->antialias) {
+    raster_bwd_f32x3_launch(a, w, s);
+  } else {
+    // every tile size of one (type, channel count)
+    auto tiles = [&](auto t, auto f) {
+      with_tile_size(cfg->tile_size, [&](auto tile_size) {
+        using T = decltype(t);
+        constexpr int F = decltype(f)::value, TS = tile_size;
+        const RasterParams<T> rp = make_raster_params<T>(a, w);
+        auto launch = [&](auto AA, auto HEUR) {
+          raster_bwd_kernel<T, F, TS, AA, HEUR><<<dim3((unsigned)w.num_tiles), dim3(TS * TS), 0, s>>>(
+              (const T*)a.points7, (const T*)a.features, a.tile_ranges, a.overlap_to_point, (const T*)a.image,
+              (const T*)a.grad_image, rp, (T*)a.grad_points7, (T*)a.grad_features, (T*)a.point_heuristic);
+        };
+        with_bool(cfg->antialias, [&](auto AA) {
+          if constexpr (F > RASTER_MAX_F) launch(AA, std::true_type{});     // (the validator admits them with heuristics only)
+          else with_bool(heur, [&](auto HEUR) { launch(AA, HEUR); });
+        });
+      });
+    };
+    if (a.f > RASTER_MAX_F) with_dtype(a.dtype, [&](auto t) { with_constant<8, 16>(a.f, [&](auto f) { tiles(t, f); }); });
+    else with_dtype(a.dtype, [&](auto t) { with_constant<1, 2, 3, 4>(a.f, [&](auto f) { tiles(t, f); }); });
+  }
+  MS_CHECK_LAUNCH();
   return 0;
 }
 
@@ -610,8 +605,12 @@ extern "C" int ms_raster_fwd(const void* points7, const void* features, const in
                              const ms_raster_config* cfg, void* out_image, void* out_alpha,
                              void* out_visibility, int tile_row_begin, int tile_row_end, int dtype,
                              void* stream) {
-  return raster_fwd_launch(points7, features, nullptr, tile_ranges, overlap_to_point, image_w, image_h, f, cfg, out_image,
-                           out_alpha, out_visibility, tile_row_begin, tile_row_end, dtype, stream);
+  RasterArgs a{};
+  a.dtype = dtype; a.f = f; a.points7 = points7; a.features = features;
+  a.tile_ranges = tile_ranges; a.overlap_to_point = overlap_to_point;
+  a.image_w = image_w; a.image_h = image_h; a.cfg = cfg; a.tile_row_begin = tile_row_begin; a.tile_row_end = tile_row_end;
+  a.out_image = out_image; a.out_alpha = out_alpha; a.out_visibility = out_visibility;
+  return raster_fwd_launch(a, (hipStream_t)stream, __func__);
 }
 
 extern "C" size_t ms_raster_split_scratch_bytes(int64_t k_capacity, int tile_size, int split_min_run, int split_seg_len) {
@@ -624,17 +623,22 @@ extern "C" int ms_raster_fwd_split(const float* points7, const float* features, 
                                    const ms_raster_config* cfg, float* out_image, float* out_alpha,
                                    float* out_visibility, void* split_scratch, int split_min_run, int split_seg_len,
                                    int tile_row_begin, int tile_row_end, void* stream) {
-  MS_CHECK_ARG(cfg && split_scratch && k_capacity >= 0 && k_capacity < (1ll << 31), "null pointer / capacity outside [0, 2^31)");
+  MS_CHECK_ARG(cfg && split_scratch && k_capacity >= 0 && k_capacity < (1ll << 31), "null pointer / k_capacity outside [0, 2^31)");
   MS_CHECK_ARG(split_min_run >= 0 && split_seg_len >= 0, "negative split parameter");
   MS_CHECK_ARG((reinterpret_cast<uintptr_t>(split_scratch) & 255) == 0, "split_scratch must be 256-byte aligned");
   if (!raster_uses_splat_rows(cfg, 3, MS_F32)) {
-    set_error("ms_raster_fwd_split: float32 RGB, plain pdf, alpha blending");
+    set_error("ms_raster_fwd_split: float32 RGB, plain pdf, alpha blending, tile 8 / 16 / 32");
     return MS_ERR_UNSUPPORTED;
   }
   const SplitScratch sc = split_scratch_carve(split_scratch, k_capacity, cfg->tile_size,
                                               split_params(cfg->tile_size, split_min_run, split_seg_len));
-  return raster_fwd_launch(points7, features, nullptr, tile_ranges, overlap_to_point, image_w, image_h, 3, cfg, out_image,
-                           out_alpha, out_visibility, tile_row_begin, tile_row_end, MS_F32, stream, &sc, nullptr);
+  RasterArgs a{};
+  a.dtype = MS_F32; a.f = 3; a.points7 = points7; a.features = features;
+  a.tile_ranges = tile_ranges; a.overlap_to_point = overlap_to_point;
+  a.image_w = image_w; a.image_h = image_h; a.cfg = cfg; a.tile_row_begin = tile_row_begin; a.tile_row_end = tile_row_end;
+  a.split = &sc;
+  a.out_image = out_image; a.out_alpha = out_alpha; a.out_visibility = out_visibility;
+  return raster_fwd_launch(a, (hipStream_t)stream, __func__);
 }
 
 namespace ms {
@@ -673,46 +677,12 @@ extern "C" int ms_raster_fwd_rows(const float* rows, const int32_t* tile_ranges,
     set_error("ms_raster_fwd_rows: splat rows serve float32 RGB, plain pdf, alpha blending, tile 8 / 16 / 32");
     return MS_ERR_UNSUPPORTED;
   }
-  return raster_fwd_launch(rows, rows, rows, tile_ranges, overlap_to_point, image_w, image_h, 3, cfg, out_image, out_alpha,
-                           out_visibility, tile_row_begin, tile_row_end, MS_F32, stream);
-}
-
-bool ms::raster_uses_splat_rows(const ms_raster_config* cfg, int f, int dtype) {
-  return dtype == MS_F32 && f == 3 && !cfg->antialias && cfg->use_alpha_blending &&
-         (cfg->tile_size == 8 || cfg->tile_size == 16 || cfg->tile_size == 32);
-}
-
-// ms_raster_fwd with the frame executor's splat-row table (frame_internal.h): the product kernels gather from it when
-// the configuration is theirs (raster_uses_splat_rows), everything else reads the dense arrays as before
-int ms::raster_fwd_launch(const void* points7, const void* features, const float* splat_rows, const int32_t* tile_ranges,
-                      const int32_t* overlap_to_point, int image_w, int image_h, int f, const ms_raster_config* cfg,
-                      void* out_image, void* out_alpha, void* out_visibility, int tile_row_begin, int tile_row_end,
-                      int dtype, void* stream, const SplitScratch* split, int32_t* long_run_word) {
-  int rc = check_raster_common(cfg, image_w, image_h, f, dtype, &tile_row_begin, &tile_row_end, "ms_raster_fwd");
-  if (rc) return rc;
-  MS_CHECK_ARG(tile_ranges && out_image && out_alpha, "null pointer");
-  if (tile_row_end <= tile_row_begin) return 0;
-  const int tiles_wide = (image_w + cfg->tile_size - 1) / cfg->tile_size;
-  const int num_tiles = (tile_row_end - tile_row_begin) * tiles_wide;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MS_F32 && f == 3 && !cfg->antialias && cfg->use_alpha_blending) {
-    void* vis = (cfg->compute_visibility && out_visibility) ? out_visibility : nullptr;
-    if (ms_raster_fwd_fast(points7, features, tile_ranges, overlap_to_point, image_w, image_h, cfg, out_image,
-                           out_alpha, vis, tile_row_begin, num_tiles, s, splat_rows, split, long_run_word)) {
-      MS_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-#define MS_GO(T, F) rc = dispatch_ts_fwd<T, F>(cfg->tile_size, points7, features, tile_ranges, overlap_to_point, image_w, image_h, cfg, out_image, out_alpha, out_visibility, tile_row_begin, num_tiles, s)
-  if (dtype == MS_F32) {
-    switch (f) { case 1: MS_GO(float, 1); break; case 2: MS_GO(float, 2); break; case 3: MS_GO(float, 3); break; default: MS_GO(float, 4); break; }
-  } else {
-    switch (f) { case 1: MS_GO(double, 1); break; case 2: MS_GO(double, 2); break; case 3: MS_GO(double, 3); break; default: MS_GO(double, 4); break; }
-  }
-#undef MS_GO
-  if (rc) return rc;
-  MS_CHECK_LAUNCH();
-  return 0;
+  RasterArgs a{};
+  a.dtype = MS_F32; a.f = 3; a.points7 = rows; a.features = rows; a.splat_rows = rows;
+  a.tile_ranges = tile_ranges; a.overlap_to_point = overlap_to_point;
+  a.image_w = image_w; a.image_h = image_h; a.cfg = cfg; a.tile_row_begin = tile_row_begin; a.tile_row_end = tile_row_end;
+  a.out_image = out_image; a.out_alpha = out_alpha; a.out_visibility = out_visibility;
+  return raster_fwd_launch(a, (hipStream_t)stream, __func__);
 }
 
 extern "C" int ms_raster_bwd(const void* points7, const void* features, const int32_t* tile_ranges,
@@ -720,41 +690,11 @@ extern "C" int ms_raster_bwd(const void* points7, const void* features, const in
                              int image_w, int image_h, int f, const ms_raster_config* cfg,
                              void* grad_points7, void* grad_features, void* point_heuristic,
                              int tile_row_begin, int tile_row_end, int dtype, void* stream) {
-  const bool wide = cfg && cfg->compute_point_heuristic && point_heuristic;
-  int rc = check_raster_common(cfg, image_w, image_h, f, dtype, &tile_row_begin, &tile_row_end, "ms_raster_bwd",
-                               wide ? RASTER_MAX_F_HEUR : RASTER_MAX_F);
-  if (rc) return rc;
-  MS_CHECK_ARG(tile_ranges && image && grad_image, "null pointer");
-  MS_CHECK_ARG(cfg->use_alpha_blending, "backward requires use_alpha_blending (reference: tests/test_rasterizer.py:92-94)");
-  if (tile_row_end <= tile_row_begin) return 0;
-  if (!grad_points7 && !grad_features && !point_heuristic) return 0;
-  const int tiles_wide = (image_w + cfg->tile_size - 1) / cfg->tile_size;
-  const int num_tiles = (tile_row_end - tile_row_begin) * tiles_wide;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MS_F32 && f == 3 && !cfg->antialias) {
-    if (ms_raster_bwd_fast(points7, features, tile_ranges, overlap_to_point, image, grad_image, image_w, image_h,
-                           cfg, grad_points7, grad_features, point_heuristic, tile_row_begin, num_tiles, s)) {
-      MS_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  if (f > RASTER_MAX_F) {
-#define MS_WIDE(T, F) rc = dispatch_ts_bwd_wide<T, F>(cfg->tile_size, points7, features, tile_ranges, overlap_to_point, image, grad_image, image_w, image_h, cfg, grad_points7, grad_features, point_heuristic, tile_row_begin, num_tiles, s)
-    if (dtype == MS_F32) { if (f == 8) MS_WIDE(float, 8); else MS_WIDE(float, 16); }
-    else { if (f == 8) MS_WIDE(double, 8); else MS_WIDE(double, 16); }
-#undef MS_WIDE
-    if (rc) return rc;
-    MS_CHECK_LAUNCH();
-    return 0;
-  }
-#define MS_GO(T, F) rc = dispatch_ts_bwd<T, F>(cfg->tile_size, points7, features, tile_ranges, overlap_to_point, image, grad_image, image_w, image_h, cfg, grad_points7, grad_features, point_heuristic, tile_row_begin, num_tiles, s)
-  if (dtype == MS_F32) {
-    switch (f) { case 1: MS_GO(float, 1); break; case 2: MS_GO(float, 2); break; case 3: MS_GO(float, 3); break; default: MS_GO(float, 4); break; }
-  } else {
-    switch (f) { case 1: MS_GO(double, 1); break; case 2: MS_GO(double, 2); break; case 3: MS_GO(double, 3); break; default: MS_GO(double, 4); break; }
-  }
-#undef MS_GO
-  if (rc) return rc;
-  MS_CHECK_LAUNCH();
-  return 0;
+  RasterArgs a{};
+  a.dtype = dtype; a.f = f; a.points7 = points7; a.features = features;
+  a.tile_ranges = tile_ranges; a.overlap_to_point = overlap_to_point;
+  a.image_w = image_w; a.image_h = image_h; a.cfg = cfg; a.tile_row_begin = tile_row_begin; a.tile_row_end = tile_row_end;
+  a.image = image; a.grad_image = grad_image;
+  a.grad_points7 = grad_points7; a.grad_features = grad_features; a.point_heuristic = point_heuristic;
+  return raster_bwd_launch(a, (hipStream_t)stream, __func__);
 }

@@ -857,76 +857,57 @@ extern "C" int ms_probe_raster_bwd(void* start_event, void* stop_event) {
   return 0;
 }
 
-static int launch_scan_backward(const float* points7, const float* features,
-                                const int32_t* tile_ranges, const int32_t* overlap_to_point, const float* image,
-                                const float* grad_image, int image_w, int image_h, const ms_raster_config* cfg,
-                                float* moments, int deterministic, const int32_t* fixed_exp, int tile_row_begin,
-                                int tile_row_end, hipStream_t s, const char* who, int grad_broadcast = 0,
-                                const float* splat_rows = nullptr, const SplitScratch* split = nullptr) {
-  if (deterministic && !fixed_exp) { set_error("%s: deterministic commits need fixed_exp (ms_fixed_point_exponents)", who); return MS_ERR_BAD_ARG; }
-  if (image_w <= 0 || image_h <= 0) { set_error("%s: bad image size", who); return MS_ERR_BAD_ARG; }
-  if (!cfg->use_alpha_blending) {
+// The moments backward of the C entry points and of the frame executor.  Launch order: per-tile kernel (bracketed by
+// the probe), then the segments of the long runs.
+int ms::raster_bwd_moments_launch(const RasterArgs& args, hipStream_t s, const char* who) {
+  // (every MS_ERR_BAD_ARG condition is reported before any MS_ERR_UNSUPPORTED one: these two, then raster_window's)
+  if (args.deterministic && !args.fixed_exp) { set_error("%s: deterministic commits need fixed_exp (ms_fixed_point_exponents)", who); return MS_ERR_BAD_ARG; }
+  if (args.cfg && !args.cfg->use_alpha_blending) {
     set_error("%s: backward requires use_alpha_blending (reference: tests/test_rasterizer.py:92-94)", who);
     return MS_ERR_BAD_ARG;
   }
-  if (cfg->antialias) { set_error("%s: antialiased pdf is served by ms_raster_bwd", who); return MS_ERR_UNSUPPORTED; }
-  const int ts = cfg->tile_size;
-  if (ts != 8 && ts != 16 && ts != 32) { set_error("%s: tile_size must be 8, 16 or 32 (got %d)", who, ts); return MS_ERR_UNSUPPORTED; }
-  const int tiles_high = (image_h + ts - 1) / ts, tiles_wide = (image_w + ts - 1) / ts;
-  if (tile_row_begin < 0) tile_row_begin = 0;
-  if (tile_row_end > tiles_high) tile_row_end = tiles_high;
-  if (tile_row_end <= tile_row_begin) return 0;
+  RasterWindow w;
+  if (const int rc = raster_window(args, who, RASTER_MAX_F, &w)) return rc;
+  if (args.cfg->antialias) { set_error("%s: antialiased pdf is served by ms_raster_bwd", who); return MS_ERR_UNSUPPORTED; }
+  if (w.empty) return 0;
 
-  FastParams rp{};
-  rp.width = image_w; rp.height = image_h; rp.tiles_wide = tiles_wide; rp.tile_begin = tile_row_begin * tiles_wide;
-  rp.clamp_max_alpha = (float)cfg->clamp_max_alpha;
-  rp.alpha_threshold = (float)cfg->alpha_threshold;
-  rp.one_minus_saturate = (float)(1.0 - cfg->saturate_threshold);
-  rp.deterministic = deterministic != 0;
-  rp.grad_broadcast = grad_broadcast != 0;
-  rp.num_tiles = (tile_row_end - tile_row_begin) * tiles_wide;
-  if (split && ts == 32 && tile32_quarters()) split = nullptr;     // (the quarter variant walks whole tile lists)
-  if (split) {
-    rp.split_min_run = split->min_run;
-    rp.split_items = split->items; rp.split_counts = split->counts; rp.split_state = split->state;
-  }
-#define MS_GO(TS, HEUR, SPLIT, ROWS) raster_bwd_scan_kernel<TS, HEUR, SPLIT, ROWS>                               \
-      <<<dim3(xcd_grid<(SPLIT > 1 ? 1 : 0)>(rp.num_tiles, SPLIT * SPLIT)), dim3(TS * TS), 0, s>>>(              \
-          ROWS ? splat_rows : points7, features, tile_ranges, overlap_to_point, image, grad_image, rp, moments, fixed_exp)
-#define MS_GO_TILE(TS, SPLIT, ROWS)                                                                             \
-  do { if (hf) MS_GO(TS, true, SPLIT, ROWS); else MS_GO(TS, false, SPLIT, ROWS); } while (0)
-  // the segments of long tile runs (the plan and the start states are the forward's: raster_common.h); dense arrays only
-#define MS_GO_SEGS(TS)                                                                                          \
-  do {                                                                                                          \
-    if (hf) raster_bwd_scan_kernel<TS, true, 1, false, true><<<dim3((unsigned)split->item_cap), dim3(TS * TS), 0, s>>>(  \
-        points7, features, tile_ranges, overlap_to_point, image, grad_image, rp, moments, fixed_exp);          \
-    else raster_bwd_scan_kernel<TS, false, 1, false, true><<<dim3((unsigned)split->item_cap), dim3(TS * TS), 0, s>>>(    \
-        points7, features, tile_ranges, overlap_to_point, image, grad_image, rp, moments, fixed_exp);          \
-  } while (0)
+  const bool quarters = args.cfg->tile_size == 32 && tile32_quarters();
+  RasterArgs a = args;
+  if (quarters) a.split = nullptr;                             // (the quarter variant walks whole tile lists)
+  const FastParams rp = make_fast_params(a, w);
+  // TS x TS threads per workgroup, PARTS x PARTS workgroups per tile; SEGS: one workgroup per segment of a long run
+  auto launch = [&](auto tile_size, auto parts, auto rows, auto segs) {
+    constexpr int TS = tile_size, PARTS = parts;
+    constexpr bool ROWS = rows, SEGS = segs;
+    auto go = [&](auto HEUR) {
+      const dim3 grid = SEGS ? dim3((unsigned)a.split->item_cap) : dim3(xcd_grid<(PARTS > 1 ? 1 : 0)>(rp.num_tiles, PARTS * PARTS));
+      raster_bwd_scan_kernel<TS, HEUR, PARTS, ROWS, SEGS><<<grid, dim3(TS * TS), 0, s>>>(
+          ROWS ? a.splat_rows : (const float*)a.points7, (const float*)a.features, a.tile_ranges, a.overlap_to_point,
+          (const float*)a.image, (const float*)a.grad_image, rp, a.moments, a.fixed_exp);
+    };
+    with_bool(a.cfg->compute_point_heuristic, go);
+  };
+  constexpr std::integral_constant<int, 1> whole{};
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
   // the splat-row table serves the one-workgroup-per-tile kernels of tile 16 and 32 (tile 8 gathers inside its pass
   // loop and measured 10 % SLOWER with the 16-byte loads; the quarter-tile variant is a fallback)
-  const bool hf = cfg->compute_point_heuristic;
+  auto per_tile = [&](auto TS) { if (a.splat_rows) launch(TS, whole, yes, no); else launch(TS, whole, no, no); };
+
   const hipEvent_t probe_start = g_probe_start, probe_stop = g_probe_stop;
   g_probe_start = g_probe_stop = nullptr;                      // one launch per arming
   if (probe_start) (void)hipEventRecord(probe_start, s);
-#define MS_PROBE_STOP() do { if (probe_stop) (void)hipEventRecord(probe_stop, s); } while (0)
-  switch (ts) {
-    case 8: MS_GO_TILE(8, 1, false); MS_PROBE_STOP(); if (split) MS_GO_SEGS(8); break;
-    case 16: if (splat_rows) MS_GO_TILE(16, 1, true); else MS_GO_TILE(16, 1, false); MS_PROBE_STOP(); if (split) MS_GO_SEGS(16); break;
-    default:
-      // tile 32: ONE 1024-thread workgroup per tile with 896-splat batches (152 KB LDS), or — MS_TILE32_BWD=quarters —
-      // four 16 x 16 quarter workgroups per tile that each stage the whole tile list
-      if (tile32_quarters()) MS_GO_TILE(16, 2, false);
-      else if (splat_rows) MS_GO_TILE(32, 1, true);
-      else MS_GO_TILE(32, 1, false);
-      MS_PROBE_STOP();
-      if (split) MS_GO_SEGS(32);
-      break;
-  }
-#undef MS_PROBE_STOP
-#undef MS_GO_SEGS
-#undef MS_GO_TILE
-#undef MS_GO
+  with_tile_size(a.cfg->tile_size, [&](auto TS) {
+    if constexpr (TS == 8) launch(TS, whole, no, no);
+    else if constexpr (TS == 16) per_tile(TS);
+    // tile 32: ONE 1024-thread workgroup per tile with 896-splat batches (152 KB LDS), or — MS_TILE32_BWD=quarters —
+    // four 16 x 16 quarter workgroups per tile that each stage the whole tile list
+    else if (quarters) launch(std::integral_constant<int, TS / 2>{}, std::integral_constant<int, 2>{}, no, no);
+    else per_tile(TS);
+    if (probe_stop) (void)hipEventRecord(probe_stop, s);
+    // the segments of long tile runs (the plan and the start states are the forward's: raster_common.h); dense arrays only
+    if (a.split) launch(TS, whole, no, yes);
+  });
   MS_CHECK_LAUNCH();
   return 0;
 }
@@ -937,10 +918,13 @@ extern "C" int ms_raster_bwd_moments(const void* points7, const void* features, 
                                      int deterministic, const int32_t* fixed_exp, int tile_row_begin,
                                      int tile_row_end, void* stream) {
   MS_CHECK_ARG(cfg && points7 && features && tile_ranges && image && grad_image && moments, "null pointer");
-  return launch_scan_backward((const float*)points7, (const float*)features, tile_ranges, overlap_to_point,
-                              (const float*)image, (const float*)grad_image, image_w, image_h, cfg, moments,
-                              deterministic, fixed_exp, tile_row_begin, tile_row_end, (hipStream_t)stream,
-                              "ms_raster_bwd_moments");
+  RasterArgs a{};
+  a.dtype = MS_F32; a.f = 3; a.points7 = points7; a.features = features;
+  a.tile_ranges = tile_ranges; a.overlap_to_point = overlap_to_point;
+  a.image_w = image_w; a.image_h = image_h; a.cfg = cfg; a.tile_row_begin = tile_row_begin; a.tile_row_end = tile_row_end;
+  a.image = image; a.grad_image = grad_image;
+  a.moments = moments; a.deterministic = deterministic; a.fixed_exp = fixed_exp;
+  return raster_bwd_moments_launch(a, (hipStream_t)stream, __func__);
 }
 
 extern "C" int ms_raster_bwd_moments_rows(const float* rows, const int32_t* tile_ranges, const int32_t* overlap_to_point,
@@ -954,9 +938,13 @@ extern "C" int ms_raster_bwd_moments_rows(const float* rows, const int32_t* tile
     set_error("ms_raster_bwd_moments_rows: tile 16, or tile 32 with one workgroup per tile");
     return MS_ERR_UNSUPPORTED;
   }
-  return launch_scan_backward(rows, rows, tile_ranges, overlap_to_point, image, grad_image, image_w, image_h, cfg, moments,
-                              deterministic, fixed_exp, tile_row_begin, tile_row_end, (hipStream_t)stream,
-                              "ms_raster_bwd_moments_rows", 0, rows);
+  RasterArgs a{};
+  a.dtype = MS_F32; a.f = 3; a.points7 = rows; a.features = rows; a.splat_rows = rows;
+  a.tile_ranges = tile_ranges; a.overlap_to_point = overlap_to_point;
+  a.image_w = image_w; a.image_h = image_h; a.cfg = cfg; a.tile_row_begin = tile_row_begin; a.tile_row_end = tile_row_end;
+  a.image = image; a.grad_image = grad_image;
+  a.moments = moments; a.deterministic = deterministic; a.fixed_exp = fixed_exp;
+  return raster_bwd_moments_launch(a, (hipStream_t)stream, __func__);
 }
 
 extern "C" int ms_raster_bwd_moments_split(const float* points7, const float* features, const int32_t* tile_ranges,
@@ -969,15 +957,21 @@ extern "C" int ms_raster_bwd_moments_split(const float* points7, const float* fe
   MS_CHECK_ARG(k_capacity >= 0 && k_capacity < (1ll << 31), "k_capacity must be in [0, 2^31)");
   MS_CHECK_ARG(split_min_run >= 0 && split_seg_len >= 0, "negative split parameter");
   MS_CHECK_ARG((reinterpret_cast<uintptr_t>(split_scratch) & 255) == 0, "split_scratch must be 256-byte aligned");
+  // (the scratch is carved for the tile size: looked at here, before the launcher's own checks)
   if (cfg->tile_size != 8 && cfg->tile_size != 16 && cfg->tile_size != 32) {
     set_error("ms_raster_bwd_moments_split: tile_size must be 8, 16 or 32 (got %d)", cfg->tile_size);
     return MS_ERR_UNSUPPORTED;
   }
   const SplitScratch sc = split_scratch_carve(const_cast<void*>(split_scratch), k_capacity, cfg->tile_size,
                                               split_params(cfg->tile_size, split_min_run, split_seg_len));
-  return launch_scan_backward(points7, features, tile_ranges, overlap_to_point, image, grad_image, image_w, image_h, cfg,
-                              moments, deterministic, fixed_exp, tile_row_begin, tile_row_end, (hipStream_t)stream,
-                              "ms_raster_bwd_moments_split", 0, nullptr, &sc);
+  RasterArgs a{};
+  a.dtype = MS_F32; a.f = 3; a.points7 = points7; a.features = features;
+  a.tile_ranges = tile_ranges; a.overlap_to_point = overlap_to_point;
+  a.image_w = image_w; a.image_h = image_h; a.cfg = cfg; a.tile_row_begin = tile_row_begin; a.tile_row_end = tile_row_end;
+  a.split = &sc;
+  a.image = image; a.grad_image = grad_image;
+  a.moments = moments; a.deterministic = deterministic; a.fixed_exp = fixed_exp;
+  return raster_bwd_moments_launch(a, (hipStream_t)stream, __func__);
 }
 
 extern "C" int ms_fixed_point_exponents(const float* amax_dev, int32_t* out_exp2, void* stream) {
@@ -1013,42 +1007,27 @@ extern "C" int ms_raster_moments_finalize(const void* points7, const float* mome
   if (n == 0) return 0;
   MS_CHECK_ARG(points7 && moments, "null pointer");
   if (!grad_points7 && !grad_features && !point_heuristic) return 0;
-  const dim3 grid((unsigned)div_up(n, 256));
-  hipStream_t s = (hipStream_t)stream;
-#define MS_GO(HEUR, FIXED) raster_moments_finalize_kernel<HEUR, FIXED><<<grid, 256, 0, s>>>(            \
-      (const float*)points7, const_cast<float*>(moments), n, grad_points7, grad_features, point_heuristic, fixed_exp)
-  if (point_heuristic) { if (deterministic) MS_GO(true, true); else MS_GO(true, false); }
-  else { if (deterministic) MS_GO(false, true); else MS_GO(false, false); }
-#undef MS_GO
-  MS_CHECK_LAUNCH();
-  return 0;
+  RasterArgs a{};
+  a.points7 = points7; a.moments = const_cast<float*>(moments); a.deterministic = deterministic; a.fixed_exp = fixed_exp;
+  a.grad_points7 = grad_points7; a.grad_features = grad_features; a.point_heuristic = point_heuristic;
+  return moments_finalize_launch(a, n, MomentsFinalizeForm{0, 0, false}, (hipStream_t)stream);
 }
 
-// frame executor (frame_internal.h): finalize + re-zero of the rows it read
-namespace ms {
-int raster_bwd_moments_launch(const void* points7, const void* features, const int32_t* tile_ranges,
-                              const int32_t* overlap_to_point, const void* image, const void* grad_image, int image_w,
-                              int image_h, const ms_raster_config* cfg, float* moments, int deterministic,
-                              const int32_t* fixed_exp, int tile_row_begin, int tile_row_end, int grad_broadcast,
-                              hipStream_t s, const float* splat_rows, const SplitScratch* split) {
-  return launch_scan_backward((const float*)points7, (const float*)features, tile_ranges, overlap_to_point,
-                              (const float*)image, (const float*)grad_image, image_w, image_h, cfg, moments,
-                              deterministic, fixed_exp, tile_row_begin, tile_row_end, s, "ms_frame_backward", grad_broadcast,
-                              splat_rows, split);
-}
-
-int moments_finalize_rezero_launch(const float* points7, float* moments, int deterministic, const int32_t* fixed_exp,
-                                   int64_t n, float* grad_points7, float* grad_features, float* point_heuristic,
-                                   hipStream_t s, int row_stride, int covariance_form) {
+int ms::moments_finalize_launch(const RasterArgs& a, int64_t n, const MomentsFinalizeForm& form, hipStream_t s) {
   if (n == 0) return 0;
   const dim3 grid((unsigned)div_up(n, 256));
-  const int gp_stride = row_stride > 0 ? row_stride : 7, gf_stride = row_stride > 0 ? row_stride : 3;
-#define MS_GO(HEUR, FIXED) raster_moments_finalize_kernel<HEUR, FIXED, true><<<grid, 256, 0, s>>>(      \
-      points7, moments, n, grad_points7, grad_features, point_heuristic, fixed_exp, gp_stride, gf_stride, covariance_form)
-  if (point_heuristic) { if (deterministic) MS_GO(true, true); else MS_GO(true, false); }
-  else { if (deterministic) MS_GO(false, true); else MS_GO(false, false); }
-#undef MS_GO
+  const int gp_stride = form.row_stride > 0 ? form.row_stride : 7, gf_stride = form.row_stride > 0 ? form.row_stride : 3;
+  auto launch = [&](auto HEUR, auto FIXED, auto REZERO) {
+    raster_moments_finalize_kernel<HEUR, FIXED, REZERO><<<grid, 256, 0, s>>>(
+        (const float*)a.points7, a.moments, n, (float*)a.grad_points7, (float*)a.grad_features, (float*)a.point_heuristic,
+        a.fixed_exp, gp_stride, gf_stride, form.covariance_form);
+  };
+  auto rows = [&](auto REZERO) {
+    with_bool(a.point_heuristic != nullptr, [&](auto HEUR) {
+      with_bool(a.deterministic != 0, [&](auto FIXED) { launch(HEUR, FIXED, REZERO); });
+    });
+  };
+  if (!form.rezero) rows(std::false_type{}); else rows(std::true_type{});
   MS_CHECK_LAUNCH();
   return 0;
 }
-}  // namespace ms

@@ -1,9 +1,12 @@
-// raster_common.h — pieces shared by the raster kernels (raster_fast.hip, and the float commit of raster.hip):
-// kernel parameters, the two-deep gather pipeline's raw record, the LDS blend / cull records, the
-// conservative rectangle-vs-contribution-ellipse test and the wave64 halving butterfly.
+// raster_common.h — pieces shared by the raster kernels (raster_fast.hip, raster_bwd_scan.hip, and the float commit of
+// raster.hip): kernel parameters and their one builder from the launch record (make_fast_params), the run-time ->
+// compile-time dispatch helper of the launchers (with_constant), the two-deep gather pipeline's raw record, the LDS
+// blend / cull records, the conservative rectangle-vs-contribution-ellipse test and the wave64 halving butterfly.
 #pragma once
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
+#include "frame_internal.h"
 
 namespace ms {
 
@@ -82,6 +85,38 @@ static inline SplitScratch split_scratch_carve(void* base, int64_t k_capacity, i
   sc.state = (float4*)p;
   return sc;
 }
+
+// The kernel parameters of the product forward, the patch backward and the scan backward from the launch record and
+// its window (frame_internal.h): the one place the record's switches reach a kernel.
+static inline FastParams make_fast_params(const RasterArgs& a, const RasterWindow& w) {
+  FastParams rp{};
+  rp.width = a.image_w; rp.height = a.image_h;
+  rp.tiles_wide = w.tiles_wide; rp.tile_begin = w.tile_begin; rp.num_tiles = w.num_tiles;
+  rp.clamp_max_alpha = (float)a.cfg->clamp_max_alpha;
+  rp.alpha_threshold = (float)a.cfg->alpha_threshold;
+  rp.one_minus_saturate = (float)(1.0 - a.cfg->saturate_threshold);
+  rp.deterministic = a.deterministic != 0;
+  rp.grad_broadcast = a.grad_broadcast != 0;
+  if (a.split) {
+    rp.split_min_run = a.split->min_run;
+    rp.split_items = a.split->items; rp.split_counts = a.split->counts; rp.split_state = a.split->state;
+  }
+  rp.long_run_word = a.long_run_word;
+  return rp;
+}
+
+// Run-time value -> compile-time constant: calls fn(std::integral_constant<int, V>{}) for the V of the list that equals
+// v, so that a launcher writes each kernel's argument list once, in a generic lambda.  raster_window has admitted only
+// listed tile sizes and feature counts.  (A LEFT fold: the lambda is instantiated in list order, and the kernels of the
+// code object follow the order of instantiation; the launchers keep the order the code object has always had.)
+template <int... Vs, typename Fn>
+static inline void with_constant(int v, Fn&& fn) {
+  (void)(... || (v == Vs && (fn(std::integral_constant<int, Vs>{}), true)));
+}
+template <typename Fn>
+static inline void with_tile_size(int tile_size, Fn&& fn) { with_constant<8, 16, 32>(tile_size, fn); }
+template <typename Fn>
+static inline void with_bool(bool b, Fn&& fn) { if (b) fn(std::true_type{}); else fn(std::false_type{}); }
 
 // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Neighbouring tiles share splats (a gaussian
 // overlaps 2.1 tiles on config D; the four quarter workgroups of a 32 x 32 tile share ALL of them), so an XCD may

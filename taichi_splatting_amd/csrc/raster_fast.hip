@@ -14,6 +14,9 @@
 //     global_atomic_add_f32 per (patch, splat) — see wave_reduce16;
 //   * the next batch's gather (overlap_to_point -> packed gaussian + colour) is issued before the
 //     current batch is consumed, hiding the dependent HBM/L2 gather latency behind the blend loop.
+//
+// Host side: raster_fwd_f32x3_launch / raster_bwd_f32x3_launch at the end of the file take the validated launch record
+// (RasterArgs + RasterWindow, frame_internal.h) from raster.hip's launchers.
 #include "raster_common.h"
 
 // The instrument (a development build: tools/build_variant.sh; profiles/r06_raster_fwd_phase_split.txt).  It measures
@@ -488,96 +491,64 @@ raster_bwd_f32x3_kernel(const float* __restrict__ points, const float* __restric
   }
 }
 
-}  // namespace ms
+// ------------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------------
+// The product forward of raster_fwd_launch (raster.hip).  Launch order: [plan of the long runs], per-tile kernel,
+// [segments, composition, segments again for the visibility].
+void raster_fwd_f32x3_launch(const RasterArgs& a, const RasterWindow& w, hipStream_t s) {
+  const FastParams rp = make_fast_params(a, w);
+  // long runs are cut when a scratch block is given; with visibility every segment is walked twice (a segment does not
+  // know the transmittance in front of it before the composition pass has run)
+  const SplitScratch* split = a.split;
+  if (split) {
+    (void)hipMemsetAsync(split->counts, 0, 4 * sizeof(int32_t), s);
+    split_plan_kernel<<<dim3((unsigned)((w.num_tiles + 255) / 256)), dim3(256), 0, s>>>(
+        a.tile_ranges, rp.tile_begin, w.num_tiles, split->min_run, split->seg_len, (int)split->item_cap, (int)split->long_cap,
+        split->counts, split->long_tiles, split->items);
+  }
+  const bool vis = a.cfg->compute_visibility && a.out_visibility, rows = a.splat_rows != nullptr;
+  const dim3 tiles(xcd_grid<FWD_XCD_CHUNK>(rp.num_tiles, 1));
+  with_tile_size(a.cfg->tile_size, [&](auto tile_size) {
+    constexpr int TS = tile_size;
+    auto launch = [&](auto VIS, auto ROWS, auto SEGS) {
+      raster_fwd_f32x3_kernel<TS, VIS, ROWS, SEGS><<<SEGS ? dim3((unsigned)split->item_cap) : tiles, dim3(TS * TS), 0, s>>>(
+          ROWS ? a.splat_rows : (const float*)a.points7, (const float*)a.features, a.tile_ranges, a.overlap_to_point, rp,
+          (float*)a.out_image, (float*)a.out_alpha, VIS ? (float*)a.out_visibility : nullptr);
+    };
+    auto segments = [&](auto VIS) { with_bool(rows, [&](auto ROWS) { launch(VIS, ROWS, std::true_type{}); }); };
+    with_bool(rows, [&](auto ROWS) { with_bool(vis, [&](auto VIS) { launch(VIS, ROWS, std::false_type{}); }); });
+    if (split) {
+      segments(std::false_type{});
+      split_combine_kernel<TS><<<dim3((unsigned)split->long_cap), dim3(TS * TS), 0, s>>>(
+          rp, split->long_tiles, (float*)a.out_image, (float*)a.out_alpha);
+      if (vis) segments(std::true_type{});
+    }
+  });
+}
 
-using namespace ms;
+// The patch backward of raster_bwd_launch (raster.hip): atomic commits, one patch per wave
+void raster_bwd_f32x3_launch(const RasterArgs& a, const RasterWindow& w, hipStream_t s) {
+  const FastParams rp = make_fast_params(a, w);
+  const dim3 grid(xcd_grid<BWD_XCD_CHUNK>(rp.num_tiles, 1));
+  with_tile_size(a.cfg->tile_size, [&](auto tile_size) {
+    constexpr int TS = tile_size;
+    auto launch = [&](auto HEUR) {
+      raster_bwd_f32x3_kernel<TS, HEUR><<<grid, dim3(TS * TS), 0, s>>>(
+          (const float*)a.points7, (const float*)a.features, a.tile_ranges, a.overlap_to_point, (const float*)a.image,
+          (const float*)a.grad_image, rp, (float*)a.grad_points7, (float*)a.grad_features, (float*)a.point_heuristic);
+    };
+    with_bool(a.cfg->compute_point_heuristic && a.point_heuristic, launch);
+  });
+}
+
+}  // namespace ms
 
 #if MS_FWD_PHASES
 // rows: device buffer of (waves of the launch) x 12 uint64 the next launches fill (NULL: stop recording)
 extern "C" int ms_debug_fwd_phases(unsigned long long* rows, int unused) {
   (void)unused;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fwd_phase_rows), &rows, sizeof(rows));
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(ms::g_fwd_phase_rows), &rows, sizeof(rows));
   return 0;
 }
 #endif
-
-static FastParams make_fast_params(int w, int h, const ms_raster_config* cfg, int row_begin, int num_tiles) {
-  FastParams rp{};
-  rp.width = w; rp.height = h;
-  rp.tiles_wide = (w + cfg->tile_size - 1) / cfg->tile_size;
-  rp.tile_begin = row_begin * rp.tiles_wide;
-  rp.clamp_max_alpha = (float)cfg->clamp_max_alpha;
-  rp.alpha_threshold = (float)cfg->alpha_threshold;
-  rp.one_minus_saturate = (float)(1.0 - cfg->saturate_threshold);
-  rp.deterministic = 0;
-  rp.num_tiles = num_tiles;
-  rp.grad_broadcast = 0;
-  return rp;
-}
-
-// Called from raster.hip's dispatch.  Returns true if the fast path handled the launch.
-bool ms_raster_fwd_fast(const void* points, const void* feats, const int32_t* ranges, const int32_t* o2p,
-                        int w, int h, const ms_raster_config* cfg, void* image, void* alpha, void* visibility,
-                        int row_begin, int num_tiles, hipStream_t s, const float* splat_rows, const SplitScratch* split,
-                        int32_t* long_run_word) {
-  FastParams rp = make_fast_params(w, h, cfg, row_begin, num_tiles);
-  rp.long_run_word = long_run_word;
-  // long runs are cut when a scratch block is given; with visibility every segment is walked twice (a segment does not
-  // know the transmittance in front of it before the composition pass has run)
-  const bool cut = split != nullptr;
-  if (cut) {
-    rp.split_min_run = split->min_run;
-    rp.split_items = split->items; rp.split_counts = split->counts; rp.split_state = split->state;
-    (void)hipMemsetAsync(split->counts, 0, 4 * sizeof(int32_t), s);
-    split_plan_kernel<<<dim3((unsigned)((num_tiles + 255) / 256)), dim3(256), 0, s>>>(
-        ranges, rp.tile_begin, num_tiles, split->min_run, split->seg_len, (int)split->item_cap, (int)split->long_cap,
-        split->counts, split->long_tiles, split->items);
-  }
-  const dim3 grid(xcd_grid<FWD_XCD_CHUNK>(rp.num_tiles, 1));
-#define MS_GO3(TS, VIS, ROWS)                                                                                   \
-  raster_fwd_f32x3_kernel<TS, VIS, ROWS><<<grid, dim3(TS * TS), 0, s>>>(                                        \
-      ROWS ? splat_rows : (const float*)points, (const float*)feats, ranges, o2p, rp, (float*)image, (float*)alpha,  \
-      VIS ? (float*)visibility : nullptr)
-#define MS_SEG(TS, VIS, ROWS)                                                                                   \
-  raster_fwd_f32x3_kernel<TS, VIS, ROWS, true><<<dim3((unsigned)split->item_cap), dim3(TS * TS), 0, s>>>(       \
-      ROWS ? splat_rows : (const float*)points, (const float*)feats, ranges, o2p, rp, (float*)image, (float*)alpha, \
-      VIS ? (float*)visibility : nullptr)
-#define MS_GO(TS)                                                                                               \
-  do {                                                                                                          \
-    if (splat_rows) { if (visibility) MS_GO3(TS, true, true); else MS_GO3(TS, false, true); }                   \
-    else { if (visibility) MS_GO3(TS, true, false); else MS_GO3(TS, false, false); }                            \
-    if (cut) {                                                                                                  \
-      if (splat_rows) MS_SEG(TS, false, true); else MS_SEG(TS, false, false);                                   \
-      split_combine_kernel<TS><<<dim3((unsigned)split->long_cap), dim3(TS * TS), 0, s>>>(                       \
-          rp, split->long_tiles, (float*)image, (float*)alpha);                                                 \
-      if (visibility) { if (splat_rows) MS_SEG(TS, true, true); else MS_SEG(TS, true, false); }                 \
-    }                                                                                                           \
-  } while (0)
-  switch (cfg->tile_size) {
-    case 8: MS_GO(8); return true;
-    case 16: MS_GO(16); return true;
-    case 32: MS_GO(32); return true;
-  }
-#undef MS_GO
-#undef MS_SEG
-#undef MS_GO3
-  return false;
-}
-
-bool ms_raster_bwd_fast(const void* points, const void* feats, const int32_t* ranges, const int32_t* o2p,
-                        const void* image, const void* grad_image, int w, int h, const ms_raster_config* cfg,
-                        void* gp, void* gf, void* heur, int row_begin, int num_tiles, hipStream_t s) {
-  const FastParams rp = make_fast_params(w, h, cfg, row_begin, num_tiles);
-  const dim3 grid(xcd_grid<BWD_XCD_CHUNK>(rp.num_tiles, 1));
-  const bool hf = cfg->compute_point_heuristic && heur;
-#define MS_GO(TS, HEUR) raster_bwd_f32x3_kernel<TS, HEUR><<<grid, dim3(TS * TS), 0, s>>>(                   \
-      (const float*)points, (const float*)feats, ranges, o2p, (const float*)image, (const float*)grad_image, \
-      rp, (float*)gp, (float*)gf, (float*)heur)
-  switch (cfg->tile_size) {
-    case 8: if (hf) MS_GO(8, true); else MS_GO(8, false); return true;
-    case 16: if (hf) MS_GO(16, true); else MS_GO(16, false); return true;
-    case 32: if (hf) MS_GO(32, true); else MS_GO(32, false); return true;
-  }
-#undef MS_GO
-  return false;
-}
