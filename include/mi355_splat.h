@@ -765,6 +765,36 @@ int ms_photometric_bwd(const void* image, const void* target, const void* map_a,
                        const void* grad_out, int H, int W, int C, int dtype, int padding, double lambda,
                        void* grad_image, void* stream);
 
+/* ---- Bilateral-grid appearance: per-image colour correction of a render, forward and backward (csrc/bilagrid.hip) ------
+ * An addition: the reference has no appearance model.  image, out, grad_out, grad_image: contiguous (H, W, 3) arrays of
+ * `dtype`, the rasterizer's layout.  grid, grad_grid: contiguous (12, L, Gy, Gx), the layout of published checkpoints;
+ * coefficient 4c + j is row c, column j of a 3 x 4 affine colour matrix.  For the pixel at row y, column x, colour
+ * p = (r, g, b):
+ *   gx = (x + 0.5) / W (Gx - 1)    gy = (y + 0.5) / H (Gy - 1)
+ *   lum = 0.299 r + 0.587 g + 0.114 b    gz = clamp(lum, 0, 1) (L - 1)
+ *   A = trilinear interpolation of the 12 planes at (gz, gy, gx): the cell along an axis is min(floor(coord), size - 2),
+ *       0 where the size is 1, and an axis of size 1 contributes its single plane with weight 1
+ *   out = A[:, :3] p + A[:, 3]
+ * which is torch's 5-D grid_sample(bilinear, padding_mode='border', align_corners=True) of the planes followed by the
+ * affine.  A NaN luminance is clamped into bin 0 (that pixel's output may be NaN, no other's), +inf into the last.
+ * ms_bilagrid_bwd, with g = grad_out and p1 = (r, g, b, 1):
+ *   grad_grid[4c + j, z, yv, xv] = sum over pixels of w_z w_y w_x g_c p1_j,  w = max(0, 1 - |coord - vertex|) on the
+ *       clamped coordinates; a vertex no pixel reaches receives exactly 0, and every element is written (the caller
+ *       need not clear the array)
+ *   grad_image = A[:, :3]^T g + [0 < lum < 1] (L - 1) (g^T (dA/dgz) p1) (0.299, 0.587, 0.114): the luminance guide is
+ *       differentiated as grid_sample does, and is flat where it is clamped
+ * grad_image NULL or grad_grid NULL skips that gradient (and its kernels).  grad_grid is a gather without atomics: a
+ * workgroup sums one vertex's weights over a chunk of its footprint into tmp (double), a second kernel adds the chunks
+ * in a fixed order: bit-reproducible.  tmp == NULL: *tmp_bytes receives the size tmp must have for these sizes (the
+ * same whichever gradients are asked for) and nothing is launched.  Neither call reads back to the host.
+ * 1 <= L <= 16, 1 <= Gy, Gx <= 128, H W 3 < 2^31.
+ * MS_ERR_BAD_ARG: null pointer, a size <= 0, both gradients NULL; MS_ERR_UNSUPPORTED: unknown dtype, sizes beyond the
+ * limits; MS_ERR_TMP_TOO_SMALL. */
+int ms_bilagrid_fwd(const void* image, const void* grid, int H, int W, int L, int Gy, int Gx, int dtype, void* out,
+                    void* stream);
+int ms_bilagrid_bwd(const void* image, const void* grid, const void* grad_out, int H, int W, int L, int Gy, int Gx,
+                    int dtype, void* grad_image, void* grad_grid, void* tmp, size_t* tmp_bytes, void* stream);
+
 /* ---- Scene transform: a similarity m = [[s R, t], [0, 1]] on a whole 3-D scene in one launch (csrc/scene_transform.hip) --
  * An addition: the reference's transform_rigid (data_types.py:91-102) moves position and rotation and leaves the SH
  * coefficients alone, so the view-dependent colour of a rotated scene points the old way.

@@ -210,6 +210,8 @@ SIGNATURES = {
   'ms_densify_split3d': (c_int, [c_void_p] * 3 + [c_int64, c_int64, c_int] + [c_void_p] * 3),
   'ms_photometric_fwd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p, c_void_p]),
   'ms_photometric_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
+  'ms_bilagrid_fwd': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p]),
+  'ms_bilagrid_bwd': (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3 + [POINTER(c_size_t), c_void_p]),
   'ms_scene_transform': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, POINTER(c_double), c_void_p]),
   'ms_camera_coverage': (c_int, [c_void_p] * 5 + [c_int, c_double, c_double, c_double, c_int64] + [c_void_p] * 4 + [c_int, c_void_p]),
   'ms_relocate_weights': (c_int, [c_void_p, c_int64, c_float] + [c_void_p] * 4),
