@@ -346,6 +346,25 @@ int ms_raster_bwd_moments_rows(const float* rows, const int32_t* tile_ranges, co
                                const ms_raster_config* cfg, float* moments, int deterministic,
                                const int32_t* fixed_exp, int tile_row_begin, int tile_row_end, void* stream);
 
+/* Wide-feature rasteriser (csrc/raster_wide.hip): (V, f) float32 features, 1 <= f <= MS_RASTER_WIDE_MAX_F, blended in
+ * ONE pass over the tile lists with the contractions on the f32-input MFMA.  Semantics of ms_raster_fwd / ms_raster_bwd
+ * with use_alpha_blending = 1, antialias = 0 on float32 at tile size 16: out_image (H, W, f), out_alpha (H, W), both
+ * written whole; the forward has no atomics (two runs are bitwise equal).  The backward ACCUMULATES into grad_points7
+ * (V, 7) and grad_features (V, f) (pre-zero them; float atomics); either may be NULL and is then not computed (without
+ * grad_points7 the geometry part of the pass is skipped altogether).  cfg->compute_visibility and
+ * cfg->compute_point_heuristic are ignored: the wide pass computes neither.  Nothing is read back, allocated or
+ * synchronised.  A tile whose range is empty renders zeros.
+ * MS_ERR_BAD_ARG: null pointer, a size <= 0, f outside 1..MS_RASTER_WIDE_MAX_F, both gradients NULL;
+ * MS_ERR_UNSUPPORTED (after every MS_ERR_BAD_ARG condition): tile size other than 16, antialias, no alpha blending. */
+#define MS_RASTER_WIDE_MAX_F 128
+int ms_raster_wide_fwd(const float* points7, const float* features, const int32_t* tile_ranges,
+                       const int32_t* overlap_to_point, int image_w, int image_h, int f, const ms_raster_config* cfg,
+                       float* out_image, float* out_alpha, void* stream);
+int ms_raster_wide_bwd(const float* points7, const float* features, const int32_t* tile_ranges,
+                       const int32_t* overlap_to_point, const float* image, const float* grad_image, int image_w,
+                       int image_h, int f, const ms_raster_config* cfg, float* grad_points7, float* grad_features,
+                       void* stream);
+
 /* ---- frame executor --------------------------------------------------------------------------------------------
  * One frame of render_gaussians (renderer.py:23-108) or rasterize (rasterizer/function.py:133-165) as a FIXED launch
  * sequence without host round trips, so that a frame can be enqueued ahead of the GPU and captured in a hipGraph:

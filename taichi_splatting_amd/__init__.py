@@ -10,6 +10,7 @@ from .rendering import Rendering, RenderedPoints
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
 from .rasterizer import rasterize, rasterize_with_tiles, RasterOut
+from .rasterizer.wide import rasterize_wide, render_features
 from .spherical_harmonics import evaluate_sh_at, sh_rotation_matrices, rotate_sh
 from . import perspective
 from . import cuda_lib
@@ -34,7 +35,7 @@ __all__ = [
   'map_to_tiles', 'pad_to_tile',
   'Gaussians2D', 'Gaussians3D',
   'RasterConfig', 'evaluate_sh_at', 'sh_rotation_matrices', 'rotate_sh',
-  'rasterize', 'rasterize_with_tiles',
+  'rasterize', 'rasterize_with_tiles', 'rasterize_wide', 'render_features',
   'perspective', 'TaichiQueue',
   'l1_ssim_loss', 'ssim',
   'load_ply', 'save_ply', 'read_ply_header',
@@ -56,7 +57,7 @@ def install_as_taichi_splatting():
   for sub in ('data_types', 'scene_io', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
-              'rasterizer.function', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'optim', 'optim.fractional', 'optim.relocate',
+              'rasterizer.function', 'rasterizer.wide', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'optim', 'optim.fractional', 'optim.relocate',
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',

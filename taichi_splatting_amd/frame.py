@@ -1015,6 +1015,7 @@ def render_frame(gaussians, camera_params, config: RasterConfig, use_sh: bool, u
   rendering = Rendering(image=image, image_weight=alpha, depth_image=None, median_depth_image=median, points=points,
                         camera=camera_params, config=config)
   object.__setattr__(rendering, 'frame', state)
+  object.__setattr__(rendering, 'frame_points7', points7)      # the node's (n, 7) output: render_features blends on it
   _settle_or_queue(state, image.requires_grad)
   return rendering
 
