@@ -814,6 +814,47 @@ int ms_bilagrid_fwd(const void* image, const void* grid, int H, int W, int L, in
 int ms_bilagrid_bwd(const void* image, const void* grid, const void* grad_out, int H, int W, int L, int Gy, int Gx,
                     int dtype, void* grad_image, void* grad_grid, void* tmp, size_t* tmp_bytes, void* stream);
 
+/* ---- Geometry: per-gaussian normals, and the normal-consistency loss of a blended geometry image (csrc/geometry.hip) ----
+ * An addition: the reference renders no normals.  float32 and float64; nothing reads back to the host; no atomics.
+ *
+ * ms_gaussian_normals_fwd: position (n, 3), log_scaling (n, 3), rotation (n, 4, xyzw, normalised on read),
+ * camera_position 3 values in DEVICE memory.  normals (n, 3): column k of R(rotation / |rotation|), k the index of the
+ * smallest log_scaling entry (a tie takes the lowest index), negated where normal . (position - camera_position) > 0
+ * (exactly 0 keeps the sign).  code (n bytes) receives k | flipped << 2, which is all the backward needs of position,
+ * log_scaling and camera_position.
+ * ms_gaussian_normals_bwd: grad_rotation (n, 4) = d(normals . grad_normals) / d rotation through the unnormalised
+ * quaternion, with k and the sign of `code` held constant.  There is no other gradient.
+ *
+ * ms_normal_consistency_fwd: accum is a contiguous (H, W, F) image whose channel depth_offset holds sum w z,
+ * alpha_offset sum w, normal_offset .. normal_offset + 2 sum w n (camera frame); projection = (fx, fy, cx, cy) in DEVICE
+ * memory; pixel centres at (x + 0.5, y + 0.5).  With d = depth_sum / alpha and P = d ((x + 0.5 - cx) / fx,
+ * (y + 0.5 - cy) / fy, 1), for 1 <= x <= W - 2, 1 <= y <= H - 2:
+ *   a = P(x + 1, y) - P(x - 1, y)    b = P(x, y + 1) - P(x, y - 1)    c = b x a   (a fronto-parallel plane: (0, 0, -1))
+ *   n_d = c / |c| where |c|^2 >= MS_NORMAL_TINY, else 0;   n^ = normal_sum / |normal_sum| under the same rule
+ *   out_loss[0] = sum of w (1 - n^ . n_d) / ((H - 2)(W - 2))
+ * w = pixel_weight (H, W), or alpha where pixel_weight is NULL, where the pixel and its four neighbours all have
+ * alpha >= alpha_min (> 0 required; d is evaluated nowhere else), and 0 elsewhere.  H < 3 or W < 3: exactly 0.
+ * depth_normals: NULL or (H, W, 3), receives n_d (0 outside the interior and where w's indicator fails).  tmp holds one
+ * double per workgroup, added in a fixed order by a second kernel: bit-reproducible.  tmp == NULL: *tmp_bytes receives the
+ * size tmp must have and nothing is launched.
+ * ms_normal_consistency_bwd: ONE launch; grad_accum (H, W, F) = grad_loss * d out_loss / d accum in the depth, alpha and
+ * normal channels, exactly 0 in every other channel; every element is written.  w is a constant, a vector under
+ * MS_NORMAL_TINY a constant 0, and there is no gradient for projection.  grad_loss is ONE value of `dtype` in DEVICE
+ * memory.
+ * MS_ERR_BAD_ARG: null pointer, a size <= 0, F < 5, channel offsets outside the image or overlapping, alpha_min <= 0;
+ * MS_ERR_UNSUPPORTED: unknown dtype, H W F >= 2^31; MS_ERR_TMP_TOO_SMALL. */
+#define MS_NORMAL_TINY 1e-30
+int ms_gaussian_normals_fwd(const void* position, const void* log_scaling, const void* rotation,
+                            const void* camera_position, int64_t n, int dtype, void* normals, void* code, void* stream);
+int ms_gaussian_normals_bwd(const void* rotation, const void* code, const void* grad_normals, int64_t n, int dtype,
+                            void* grad_rotation, void* stream);
+int ms_normal_consistency_fwd(const void* accum, const void* pixel_weight, const void* projection, int H, int W, int F,
+                              int depth_offset, int alpha_offset, int normal_offset, int dtype, double alpha_min,
+                              void* tmp, size_t* tmp_bytes, void* out_loss, void* depth_normals, void* stream);
+int ms_normal_consistency_bwd(const void* accum, const void* pixel_weight, const void* projection, const void* grad_loss,
+                              int H, int W, int F, int depth_offset, int alpha_offset, int normal_offset, int dtype,
+                              double alpha_min, void* grad_accum, void* stream);
+
 /* ---- Scene transform: a similarity m = [[s R, t], [0, 1]] on a whole 3-D scene in one launch (csrc/scene_transform.hip) --
  * An addition: the reference's transform_rigid (data_types.py:91-102) moves position and rotation and leaves the SH
  * coefficients alone, so the view-dependent colour of a rotated scene points the old way.

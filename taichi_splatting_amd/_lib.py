@@ -214,6 +214,10 @@ SIGNATURES = {
   'ms_photometric_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
   'ms_bilagrid_fwd': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p]),
   'ms_bilagrid_bwd': (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3 + [POINTER(c_size_t), c_void_p]),
+  'ms_gaussian_normals_fwd': (c_int, [c_void_p] * 4 + [c_int64, c_int] + [c_void_p] * 3),
+  'ms_gaussian_normals_bwd': (c_int, [c_void_p] * 3 + [c_int64, c_int] + [c_void_p] * 2),
+  'ms_normal_consistency_fwd': (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_double, c_void_p, POINTER(c_size_t)] + [c_void_p] * 3),
+  'ms_normal_consistency_bwd': (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_double, c_void_p, c_void_p]),
   'ms_scene_transform': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, POINTER(c_double), c_void_p]),
   'ms_camera_coverage': (c_int, [c_void_p] * 5 + [c_int, c_double, c_double, c_double, c_int64] + [c_void_p] * 4 + [c_int, c_void_p]),
   'ms_relocate_weights': (c_int, [c_void_p, c_int64, c_float] + [c_void_p] * 4),
