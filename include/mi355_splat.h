@@ -277,9 +277,22 @@ int ms_raster_bwd(const void* points7, const void* features, const int32_t* tile
  * dL/dimage: ms_fixed_point_exponents turns max |grad_image| (one float in device memory, e.g. torch's amax) into
  * the two binary exponents `fixed_exp` (device, int32[2]: sums linear in dL/dimage; the squared prune-cost sum)
  * that both functions then read — no host round trip.  Pass the same flag and exponents to both functions.
- * ms_raster_moments_finalize writes exact zeros for splats that can never blend (alpha or a sigma of 0). */
+ * ms_raster_moments_finalize writes exact zeros for splats that can never blend (alpha or a sigma of 0).
+ *
+ * Headroom.  ms_fixed_point_exponents looks at max |grad_image| alone: e_main = 36 - e, e_h0 = 36 - 2 e with
+ * amax = f 2^e, both clamped to [-100, 100].  A row then holds 2^63 units = amax 2^27 for the linear columns 0..8 and
+ * 10 and amax^2 2^29 for column 9, whatever the colours and the number of pixels a splat covers; beyond that it WRAPS,
+ * silently (a splat over a 256 x 256 image with colours of ~4000, or over 4096 x 4096 with colours of ~16).  It is kept
+ * for existing callers.  ms_fixed_point_exponents_ranged also takes max |feature|, the smallest positive sigma of
+ * points7 (stats3_dev: {max |grad_image|, max |feature|, min sigma}, three floats in device memory), the pixel count of
+ * the launch window and alpha_threshold, bounds every column from them and coarsens a unit by exactly the bits by which
+ * a row could otherwise pass 2^61 units — by none where the units above already fit ("Range of the
+ * fixed-point rows"; it assumes alpha <= 1).  Scaling grad_image by 2^k moves both forms' exponents by exactly -k / -2k.
+ * A max |feature| that is NaN or infinite is taken as the largest float, a sigma that is not positive and finite as 1. */
 #define MS_MOMENT_ROW 16
 int ms_fixed_point_exponents(const float* amax_dev, int32_t* out_exp2, void* stream);
+int ms_fixed_point_exponents_ranged(const float* stats3_dev, int64_t pixels, float alpha_threshold,
+                                    int32_t* out_exp2, void* stream);
 int ms_raster_bwd_moments(const void* points7, const void* features, const int32_t* tile_ranges,
                           const int32_t* overlap_to_point, const void* image, const void* grad_image,
                           int image_w, int image_h, const ms_raster_config* cfg, float* moments,

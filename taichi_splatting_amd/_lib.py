@@ -184,6 +184,7 @@ SIGNATURES = {
   'ms_fractional_update': (c_int, [c_int, c_int] + [c_void_p] * 11 + [c_int64, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p]),
   'ms_raster_fwd': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, POINTER(RasterConfigC)] + [c_void_p] * 3 + [c_int, c_int, c_int, c_void_p]),
   'ms_fixed_point_exponents': (c_int, [c_void_p, c_void_p, c_void_p]),
+  'ms_fixed_point_exponents_ranged': (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p]),
   'ms_raster_bwd_moments': (c_int, [c_void_p] * 6 + [c_int, c_int, POINTER(RasterConfigC), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
   'ms_raster_moments_finalize': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
   'ms_raster_split_scratch_bytes': (c_size_t, [c_int64, c_int, c_int, c_int]),
@@ -319,4 +320,22 @@ def fixed_point_exponents(grad_image: torch.Tensor) -> torch.Tensor:
   out = torch.empty((2,), dtype=torch.int32, device=grad_image.device)
   check(load().ms_fixed_point_exponents(amax.data_ptr(), out.data_ptr(), current_stream(grad_image.device)),
         "fixed_point_exponents")
+  return out
+
+
+def fixed_point_exponents_ranged(grad_image: torch.Tensor, points7: torch.Tensor, features: torch.Tensor, pixels: int,
+                                 alpha_threshold: float) -> torch.Tensor:
+  """``fixed_point_exponents`` with the headroom of the int64 rows taken into account (include/mi355_splat.h): the units
+  also follow max |feature|, the smallest positive sigma of ``points7`` and the pixel count of the launch window, each
+  reduced on the device (a max / min does not depend on the order of its operands: the rows stay bitwise reproducible);
+  no host read.  Rows that cannot blend (culled: NaN or zero sigma, non-finite colours) do not enter the statistics."""
+  amax = grad_image.detach().abs().amax().to(torch.float32)
+  feats = features.detach()
+  fmax = torch.where(torch.isfinite(feats), feats.abs(), torch.zeros_like(feats)).amax().to(torch.float32)
+  sigma = points7.detach()[:, 4:6]
+  smin = torch.where(sigma > 0, sigma, torch.full_like(sigma, float('inf'))).amin().to(torch.float32)
+  stats = torch.stack([amax, fmax, smin])
+  out = torch.empty((2,), dtype=torch.int32, device=grad_image.device)
+  check(load().ms_fixed_point_exponents_ranged(stats.data_ptr(), int(pixels), float(alpha_threshold), out.data_ptr(),
+                                               current_stream(grad_image.device)), "fixed_point_exponents_ranged")
   return out

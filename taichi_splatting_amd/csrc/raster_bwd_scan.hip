@@ -103,6 +103,35 @@ __global__ void fixed_point_exponents_kernel(const float* __restrict__ amax, int
   out[1] = e_h0 < -100 ? -100 : (e_h0 > 100 ? 100 : e_h0);
 }
 
+// The units above leave a row 2^63 / 2^36 = 2^27 commits of the size of max|dL/dimage| (2^29 of its square for
+// prune_cost), whatever the colours and however many pixels a splat covers: a background splat with colours ~1e3 wraps
+// its row.  The ranged form bounds every column from what the launch knows ("Range of the fixed-point rows")
+//   per pixel  |dL/dalpha| < 6 amax fmax,   X'^2 + Y'^2 < L = log2(1 / alpha_threshold)   (alpha <= 1),
+//              |tx| + |ty| <= 2 sqrt(log2(e) / 2) sqrt(L) / sigma_min                     (split_score),
+//   per row    at most `pixels` such terms
+// in whole binary exponents (frexp: x < 2^e), so that a host mirror reproduces it exactly, and makes the unit coarser
+// by exactly the bits by which a row could pass 2^61 units — by nothing where today's unit already fits.
+// stats = {max|dL/dimage|, max|feature|, smallest positive sigma}; log2_pixels = ceil(log2(pixels));
+// log2_L = ceil(log2(max(L, 1))) (both from the host: they depend on no device data).
+__global__ void fixed_point_exponents_ranged_kernel(const float* __restrict__ stats, int log2_pixels, int log2_L,
+                                                    int32_t* __restrict__ out) {
+  const float m = stats[0], fmax = stats[1], smin = stats[2];
+  int e = 0, e_f = 0, e_s = 1;
+  if (m > 0.0f && m < __builtin_inff()) (void)frexpf(m, &e);
+  const bool f_known = fmax >= 0.0f && fmax < __builtin_inff();     // (NaN / inf: no bound; assume the largest float)
+  if (!f_known) e_f = 128;
+  else if (fmax > 0.0f) (void)frexpf(fmax, &e_f);
+  if (smin > 0.0f && smin < __builtin_inff()) (void)frexpf(smin, &e_s);        // 1 / sigma <= 2^(1 - e_s)
+  const int geom = max(log2_L, 2 + (log2_L + 1) / 2 - e_s);                    // q -> the largest of columns 0..5 and 10
+  const int h_main = (f_known && fmax == 0.0f) ? 0 : max(0, 3 + e_f + geom);   // columns 6..8: |w G| <= amax
+  const int h_h0 = (f_known && fmax == 0.0f) ? 0 : max(0, 6 + 2 * e_f);
+  constexpr int FREE_BITS = 61 - FIXED_POINT_BITS;                             // 25
+  int e_main = FIXED_POINT_BITS - e - max(0, h_main + log2_pixels - FREE_BITS);
+  int e_h0 = FIXED_POINT_BITS - 2 * e - max(0, h_h0 + log2_pixels - FREE_BITS);
+  out[0] = e_main < -100 ? -100 : (e_main > 100 ? 100 : e_main);
+  out[1] = e_h0 < -100 ? -100 : (e_h0 > 100 ? 100 : e_h0);
+}
+
 // SPLIT: the mapper's tile is (TS * SPLIT)^2 pixels and SPLIT^2 workgroups share its splat list, each taking one
 // TS x TS quarter.  Tile 32 runs as <16, HEUR, 2>: with one 1024-thread workgroup per tile a staged splat touches
 // few of the 16 patches and the per-wave lists stay short (4.0 ms on config D against 1.5 ms at tile 16); a
@@ -977,6 +1006,24 @@ extern "C" int ms_raster_bwd_moments_split(const float* points7, const float* fe
 extern "C" int ms_fixed_point_exponents(const float* amax_dev, int32_t* out_exp2, void* stream) {
   MS_CHECK_ARG(amax_dev && out_exp2, "null pointer");
   fixed_point_exponents_kernel<<<1, 1, 0, (hipStream_t)stream>>>(amax_dev, out_exp2);
+  MS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ms_fixed_point_exponents_ranged(const float* stats3_dev, int64_t pixels, float alpha_threshold,
+                                               int32_t* out_exp2, void* stream) {
+  MS_CHECK_ARG(stats3_dev && out_exp2, "null pointer");
+  MS_CHECK_ARG(pixels >= 0, "negative pixel count");
+  int log2_pixels = 0;
+  while (log2_pixels < 62 && (1ll << log2_pixels) < pixels) ++log2_pixels;
+  // L = log2(1 / alpha_threshold) bounds X'^2 + Y'^2 of a pair that passes the blend gate; without a gate (threshold <= 0)
+  // exp2 itself underflows beyond 150 + the bits of a denormal
+  double L = alpha_threshold > 0.0f ? -log2((double)alpha_threshold) : 160.0;
+  if (!(L >= 1.0)) L = 1.0;
+  if (L > 160.0) L = 160.0;
+  int log2_L = 0;
+  while ((double)(1 << log2_L) < L) ++log2_L;
+  fixed_point_exponents_ranged_kernel<<<1, 1, 0, (hipStream_t)stream>>>(stats3_dev, log2_pixels, log2_L, out_exp2);
   MS_CHECK_LAUNCH();
   return 0;
 }

@@ -430,13 +430,16 @@ def backward_mode(desc):
   return bool(_lib.load().ms_frame_uses_moments(ctypes.byref(desc), int(det))), det
 
 
-def attach_moments(gr, g_image, device, n, det):
-  """Point the grads struct of a moments-path backward at its accumulator; returns what must stay alive until the launch"""
+def attach_moments(gr, g_image, device, n, det, points7, colours, size, config):
+  """Point the grads struct of a moments-path backward at its accumulator; returns what must stay alive until the launch.
+  ``points7`` (n, 7), ``colours`` (n, 3): what the raster backward reads (looked at when ``det`` only); ``size``: (width,
+  height) of the image, which holds every launch window — with ``config.alpha_threshold`` what the range of the
+  deterministic rows depends on."""
   gr.moments = _moments_buffer(device, n, det).data_ptr()
   gr.deterministic = int(det)
   if not det:
     return None
-  fixed_exp = _lib.fixed_point_exponents(g_image)
+  fixed_exp = _lib.fixed_point_exponents_ranged(g_image, points7, colours, int(size[0]) * int(size[1]), config.alpha_threshold)
   gr.fixed_exp = fixed_exp.data_ptr()
   return fixed_exp
 
@@ -809,7 +812,11 @@ class _FrameFunction(torch.autograd.Function):
 
     grad_points7 = grad_colours = None
     if moments_path:
-      fixed_exp = attach_moments(gr, g_image, device, n, det)      # noqa: F841 (alive until the launch)
+      splats = (None, None)      # (what the raster backward reads: looked at for the range of the deterministic rows only)
+      if det:
+        splats = (block_view(state.keep_n, state.layout.points7, dtype, (n, 7)),
+                  block_view(state.keep_n, state.layout.colours, dtype, (n, f)) if opts.use_sh else feat)
+      fixed_exp = attach_moments(gr, g_image, device, n, det, *splats, (image.shape[1], image.shape[0]), config)      # noqa: F841 (alive until the launch)
       if want_points:
         grad_points7 = torch.empty((n, 7), dtype=dtype, device=device)
       if want_colours:
@@ -932,7 +939,7 @@ class _RasterizeFrameFunction(torch.autograd.Function):
     gr.image, gr.grad_image = image.data_ptr(), g_image.data_ptr()
     gr.grad_points7, gr.grad_colours = gp.data_ptr(), gf.data_ptr()
     if moments_path:
-      fixed_exp = attach_moments(gr, g_image, device, n, det)      # noqa: F841 (alive until the launch)
+      fixed_exp = attach_moments(gr, g_image, device, n, det, p, feats, ctx.size, config)      # noqa: F841 (alive until the launch)
     if heuristic is not None:
       if not moments_path:
         heuristic.zero_()         # the generic kernels add; every pass leaves its own heuristics, as the moments path does

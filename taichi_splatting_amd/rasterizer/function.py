@@ -164,7 +164,8 @@ class _RasterFunction(torch.autograd.Function):
     if moments_path:
       det = int(DETERMINISTIC_BACKWARD)
       moments = torch.zeros((n, _lib.MOMENT_ROW), dtype=torch.int64 if det else torch.float32, device=gaussians.device)
-      fixed_exp = _lib.fixed_point_exponents(grad_image) if det else None
+      fixed_exp = _lib.fixed_point_exponents_ranged(grad_image, gaussians, features, window.w * window.h,
+                                                    config.alpha_threshold) if det else None
       _lib.check(lib.ms_raster_bwd_moments(gaussians.data_ptr(), features.data_ptr(), ctx.tile_overlap_ranges.data_ptr(),
                                            _lib.ptr(ctx.overlap_to_point), window.base(image, f), window.base(grad_image, f),
                                            window.w, window.h, cfg_c, moments.data_ptr(), det, _lib.ptr(fixed_exp),

@@ -223,12 +223,14 @@ class _RankStep:
       torch.cuda.synchronize()
       self.poll()
 
-  def _raster_backward_mode(self, desc, gr, g_image, device, rows_n):
+  def _raster_backward_mode(self, desc, gr, g_image, device, rows_n, points7, colours):
     """moments path + deterministic commits as frame.py does it (``rasterizer.function.DETERMINISTIC_BACKWARD`` /
-    MS_DETERMINISTIC is honoured on the rank steps too)"""
+    MS_DETERMINISTIC is honoured on the rank steps too).  ``points7`` / ``colours``: callables that give the arrays the
+    raster backward reads; called in deterministic mode only (the range of the fixed-point rows depends on them)"""
     moments_path, det = frame.backward_mode(desc)
     if moments_path:
-      self._fixed_exp = frame.attach_moments(gr, g_image, device, rows_n, det)
+      splats = (points7(), colours()) if det else (None, None)
+      self._fixed_exp = frame.attach_moments(gr, g_image, device, rows_n, det, *splats, self.image_size, self.config)
       gr.boundary_form = _lib.BOUNDARY_COVARIANCE      # the strips hand over dL/d(2D covariance): see include/mi355_splat.h
     return moments_path, det
 
@@ -298,7 +300,9 @@ class StripStep(_RankStep):
 
     # raster backward of the strip -> (n, 7 + f) 2D-boundary gradients -> sum over the strips
     gr = _lib.FrameGradsC()
-    moments_path, det = self._raster_backward_mode(desc, gr, g_image, device, n)
+    moments_path, det = self._raster_backward_mode(
+      desc, gr, g_image, device, n, lambda: frame.block_view(keep_n, lay.points7, dtype, (n, 7)),
+      lambda: frame.block_view(keep_n, lay.colours, dtype, (n, f)) if degree >= 0 else feat)
     width = 7 + f
     rows = (n + self.world - 1) // self.world * self.world
     es = image.element_size()
@@ -514,7 +518,7 @@ class ShardedStep(_RankStep):
 
     # ---- backward: strip raster -> gradients of the received rows -> home -> per-gaussian pass ---------------------
     gr = _lib.FrameGradsC()
-    moments_path, det = self._raster_backward_mode(desc_b, gr, g_image, device, m)
+    moments_path, det = self._raster_backward_mode(desc_b, gr, g_image, device, m, lambda: g2, lambda: f2)
     g_keep = self._raster_backward_images(gr, image, g_image, moments_path, f)      # noqa: F841 (alive until the launch)
     gr.stage = _lib.BACKWARD_RASTER
     bw = 7 + f

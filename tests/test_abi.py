@@ -125,6 +125,15 @@ def test_frame_calls_reject_structs_of_another_abi(lib):
     _lib.check(-4, "frame")
 
 
+def test_fixed_point_exponent_entry_points_check_their_arguments(lib):
+  """both forms of the unit selection of the deterministic raster backward (host-side checks, before any launch)"""
+  assert lib.ms_fixed_point_exponents(None, 1, None) == -1 and lib.ms_fixed_point_exponents(1, None, None) == -1
+  assert lib.ms_fixed_point_exponents_ranged(None, 100, 0.01, 1, None) == -1
+  assert lib.ms_fixed_point_exponents_ranged(1, 100, 0.01, None, None) == -1
+  assert lib.ms_fixed_point_exponents_ranged(1, -1, 0.01, 1, None) == -1
+  assert b'pixel' in lib.ms_last_error_string()
+
+
 def test_split_parameters_size_the_scratch(lib):
   """ms_raster_split_scratch_bytes with run-time (min run, segment length): smaller thresholds need more plan / state
   rows; 0 = the defaults; invalid arguments give 0 / MS_ERR_BAD_ARG (host-side checks, no GPU)."""

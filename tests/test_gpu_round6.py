@@ -124,17 +124,19 @@ def report_rows(what, got, want, p, ranges, o2p, size, cfg, tol=TOL, flagged=Non
   return entry
 
 
-def finalize(lib, p, mom, heuristics, stream):
+def finalize(lib, p, mom, heuristics, stream, deterministic=0, fixed_exp=None):
   n = p.shape[0]
   gp, gf = torch.empty((n, 7), device=DEV), torch.empty((n, 3), device=DEV)
   heur = torch.empty((n, 2), device=DEV) if heuristics else None
-  _lib.check(lib.ms_raster_moments_finalize(p.data_ptr(), mom.data_ptr(), 0, None, n, gp.data_ptr(), gf.data_ptr(),
-                                            _lib.ptr(heur), stream), "finalize")
+  _lib.check(lib.ms_raster_moments_finalize(p.data_ptr(), mom.data_ptr(), deterministic, _lib.ptr(fixed_exp), n, gp.data_ptr(),
+                                            gf.data_ptr(), _lib.ptr(heur), stream), "finalize")
   return gp, gf, heur
 
 
-def split_forward_backward(lib, p, f, o2p, ranges, size, cfg, G, min_run, seg_len, k_capacity=None):
-  """ms_raster_fwd_split + ms_raster_bwd_moments_split + ms_raster_moments_finalize through the C-ABI"""
+def split_forward_backward(lib, p, f, o2p, ranges, size, cfg, G, min_run, seg_len, k_capacity=None, deterministic=0,
+                           fixed_exp=None, rows_out=None):
+  """ms_raster_fwd_split + ms_raster_bwd_moments_split + ms_raster_moments_finalize through the C-ABI.  ``deterministic``
+  with ``fixed_exp`` (device int32[2]): int64 rows committed in fixed point; ``rows_out``: a list the raw rows are appended to"""
   (w, h), tile, n = size, cfg.tile_size, p.shape[0]
   k = o2p.shape[0] if k_capacity is None else k_capacity
   cfg_c, stream = _lib.raster_config_c(cfg), _lib.current_stream(torch.device(DEV))
@@ -146,11 +148,13 @@ def split_forward_backward(lib, p, f, o2p, ranges, size, cfg, G, min_run, seg_le
                                      image.data_ptr(), alpha.data_ptr(), _lib.ptr(vis), scratch.data_ptr(), min_run, seg_len,
                                      0, th, stream), "fwd split")
   counts = scratch[:16].view(torch.int32).cpu()
-  mom = torch.zeros((n, _lib.MOMENT_ROW), device=DEV)
+  mom = torch.zeros((n, _lib.MOMENT_ROW), dtype=torch.int64 if deterministic else torch.float32, device=DEV)
   _lib.check(lib.ms_raster_bwd_moments_split(p.data_ptr(), f.data_ptr(), ranges.data_ptr(), o2p.data_ptr(), k, image.data_ptr(),
-                                             G.data_ptr(), w, h, cfg_c, mom.data_ptr(), 0, None, scratch.data_ptr(), min_run,
-                                             seg_len, 0, th, stream), "bwd split")
-  gp, gf, heur = finalize(lib, p, mom, cfg.compute_point_heuristic, stream)
+                                             G.data_ptr(), w, h, cfg_c, mom.data_ptr(), deterministic, _lib.ptr(fixed_exp),
+                                             scratch.data_ptr(), min_run, seg_len, 0, th, stream), "bwd split")
+  if rows_out is not None:
+    rows_out.append(mom.clone())
+  gp, gf, heur = finalize(lib, p, mom, cfg.compute_point_heuristic, stream, deterministic, fixed_exp)
   return image, alpha, vis, gp, gf, heur, counts
 
 
