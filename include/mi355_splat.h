@@ -1059,6 +1059,64 @@ int ms_sh_coded_bwd(const float* positions, const float* cam_pos, const float* o
                     int k, int sh_degree, float* g_dc /* may be NULL */, float* g_codebook /* may be NULL */, void* tmp,
                     size_t* tmp_bytes, void* stream);
 
+/* ---- TSDF fusion and marching tetrahedra: depth frames -> volume -> triangle mesh (csrc/tsdf.hip; an addition) ---------
+ * The volume: tsdf and weight (nz, ny, nx) float32, colour (nz, ny, nx, 3) float32 or NULL, x fastest; sample (i, j, k)
+ * sits at origin + voxel_size (i, j, k), evaluated in float32 as o + v * (float)i per axis.  origin_host is a HOST array
+ * of 3 doubles; it, voxel_size, truncation, max_weight and min_weight are rounded to float32 once.  Every dim >= 1 and
+ * nx ny nz <= MS_TSDF_MAX_SAMPLES = 2^27: 7 possible vertices and 12 possible triangles per cell then fit the int32
+ * scans.  No call allocates, synchronises, reads device memory on the host or uses an atomic: each captures into a graph
+ * and two runs are bitwise equal.  MS_ERR_BAD_ARG (before any launch): dims outside the limits, voxel_size or truncation
+ * not > 0, max_weight not > 0, NaN min_weight, num_cameras outside 1..MS_COVERAGE_MAX_CAMERAS, an empty image, a NULL or
+ * misaligned pointer (16 bytes for tsdf, weight and colour of ms_tsdf_integrate, 4 for the rest), colour without image or
+ * image without colour.
+ *
+ * ms_tsdf_integrate: ONE launch for num_cameras frames.  depth (C, H, W) camera-z depth, 0 where uncovered;
+ * pixel_weight (C, H, W) or NULL (all 1); image (C, H, W, 3), given exactly when colour is; cameras (C, 20) float32 DEVICE
+ * rows of MS_COVERAGE_CAMERA_VALUES values as for ms_camera_coverage (the width and height of the rows are not read: all
+ * frames share the call's).  For every sample p and c = 0 .. C - 1 in that order, float32, no FMA contraction, sums left
+ * to right:
+ *   (x, y, z) = T_camera_world[c][:3] (p, 1)                                       skip unless near <= z <= far
+ *   u = fx x / z + cx, v = fy y / z + cy, ix = floor(u), iy = floor(v)             skip unless 0 <= ix < W, 0 <= iy < H
+ *   d = depth[c, iy, ix]                                                           skip unless d > 0 and finite
+ *   w = pixel_weight[c, iy, ix] or 1                                               skip unless w > 0
+ *   s = d - z                                                                      skip if s < -truncation
+ *   t = min(1, s / truncation);  W' = weight + w;  tsdf = (weight tsdf + w t) / W';  colour likewise with
+ *   image[c, iy, ix];  weight = min(W', max_weight)          (max_weight = +infinity: no clamp)
+ * A skipped sample keeps the bits of its three fields.  A lane owns MS_TSDF_RUN consecutive samples and keeps them in
+ * registers over the camera loop: the volume is read and written at most once per call, so C frames in one call equal C
+ * calls in the same order bit for bit.  Each wave tests the box of its samples against every camera's clip range and
+ * frustum (MS_TSDF_CAMERA_CHUNK cameras per ballot; conservative) and touches the volume only if a camera is left.
+ *
+ * ms_tsdf_classify / ms_tsdf_emit: marching tetrahedra on the Kuhn split of each cell into the six corner paths
+ * (0,0,0) -> (1,1,1), one per axis permutation, in lexicographic order of the permutation.  A sample is valid iff
+ * weight > 0 and weight >= min_weight, inside iff tsdf < 0; a tetrahedron emits only when its four corners are valid.
+ * A mesh vertex lies on a grid edge o -> o + d with both ends valid and of different sign, owned by o, edge types 0..6 =
+ * d in the order 100 010 001 110 101 011 111 (x y z bits), at p_o + l (p_b - p_o), l = t_o / (t_o - t_b); colour with the
+ * same l.  Vertices are ordered by (linear index of o, type), triangles by (linear index of the cell's lower corner,
+ * tetrahedron, triangle); (b - a) x (c - a) points to the positive side.  Per tetrahedron with path corners 0..3: one
+ * corner a apart from b < c < d gives (ab, ac, ad); inside a < b and outside c < d give (ac, bd, bc) then (ac, ad, bd);
+ * the last two of a triple are swapped as orientation demands (csrc/tsdf.hip).
+ *   classify: word[o] = mask (7 bits) | triangles of cell o << 8; vertex_count[o] = popcount(mask), triangle_count[o]:
+ *             the inputs of two ms_exclusive_scan_i32 (which may run in place: out == in needs n + 1 entries).
+ *   emit:     vertices of o at vertex_scan[o] + rank, triangles of cell o from triangle_scan[o]; a triangle finds a
+ *             vertex as vertex_scan[owner] + popcount(word[owner] & ((1 << type) - 1)).  out_vertices (V, 3),
+ *             out_faces (T, 3) int32, out_colours (V, 3) or NULL.  The caller sizes them from the scans' totals — the
+ *             one host read of an extraction — and skips the call when V = 0.
+ * Scratch: 12 bytes per sample (word and the two scans, n + 1 entries each) + the scan's tmp. */
+#define MS_TSDF_MAX_SAMPLES (1 << 27)
+#define MS_TSDF_RUN 4
+#define MS_TSDF_CAMERA_CHUNK 64
+int ms_tsdf_integrate(float* tsdf, float* weight, float* colour /* may be NULL */, int nx, int ny, int nz,
+                      const double* origin_host, double voxel_size, double truncation, double max_weight,
+                      const float* depth, const float* pixel_weight /* may be NULL */, const float* image /* may be NULL */,
+                      const float* cameras, int num_cameras, int width, int height, void* stream);
+int ms_tsdf_classify(const float* tsdf, const float* weight, int nx, int ny, int nz, double min_weight, int32_t* word,
+                     int32_t* vertex_count, int32_t* triangle_count, void* stream);
+int ms_tsdf_emit(const float* tsdf, const float* weight, const float* colour /* may be NULL */, int nx, int ny, int nz,
+                 const double* origin_host, double voxel_size, double min_weight, const int32_t* word,
+                 const int32_t* vertex_scan, const int32_t* triangle_scan, float* out_vertices, int32_t* out_faces,
+                 float* out_colours /* may be NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ from .scene_codec import compress_scene, load_compressed, CompressedScene, rende
 from .spherical_harmonics import evaluate_sh_coded, make_coded_sh_plan, CodedSHPlan
 from .appearance import apply_bilateral_grid, BilateralGrids, identity_bilateral_grid, bilateral_grid_tv
 from .geometry import gaussian_normals, render_geometry, GeometryImages, normal_consistency_loss, normal_consistency
+from .fusion import TSDFVolume, TriangleMesh, save_mesh_ply, fuse_scene
 
 __version__ = '0.5.1'       # = MS_VERSION 501 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -47,6 +48,7 @@ __all__ = [
   'render_compressed', 'evaluate_sh_coded', 'make_coded_sh_plan', 'CodedSHPlan',
   'apply_bilateral_grid', 'BilateralGrids', 'identity_bilateral_grid', 'bilateral_grid_tv',
   'gaussian_normals', 'render_geometry', 'GeometryImages', 'normal_consistency_loss', 'normal_consistency',
+  'TSDFVolume', 'TriangleMesh', 'save_mesh_ply', 'fuse_scene',
 ]
 
 
@@ -59,7 +61,7 @@ def install_as_taichi_splatting():
   for sub in ('data_types', 'scene_io', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
-              'rasterizer.function', 'rasterizer.wide', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'geometry', 'optim', 'optim.fractional', 'optim.relocate',
+              'rasterizer.function', 'rasterizer.wide', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'geometry', 'fusion', 'optim', 'optim.fractional', 'optim.relocate',
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',

@@ -37,6 +37,9 @@ KMEANS_MAX_D, KMEANS_MAX_K = 64, 65536   # MS_KMEANS_MAX_D / MS_KMEANS_MAX_K
 KMEANS_CHUNK = 128              # MS_KMEANS_CHUNK: codes a workgroup of ms_kmeans_assign stages per pass
 KMEANS_UPDATE_CHUNK = 1024      # MS_KMEANS_UPDATE_CHUNK: sorted entries per workgroup of ms_kmeans_update
 SH_CODED_CHUNK = 512            # MS_SH_CODED_CHUNK: entries of the code order per workgroup of ms_sh_coded_bwd
+TSDF_MAX_SAMPLES = 1 << 27        # MS_TSDF_MAX_SAMPLES: nx ny nz of a TSDF volume
+TSDF_RUN = 4                      # MS_TSDF_RUN: consecutive samples a lane of ms_tsdf_integrate owns
+TSDF_CAMERA_CHUNK = 64            # MS_TSDF_CAMERA_CHUNK: cameras a wave of ms_tsdf_integrate culls per ballot
 RELOCATE_COPY, RELOCATE_ZERO_TOUCHED, RELOCATE_INHERIT, RELOCATE_OPACITY, RELOCATE_SCALE = range(5)   # MS_RELOCATE_*
 
 _lib: Optional[ctypes.CDLL] = None
@@ -230,6 +233,9 @@ SIGNATURES = {
   'ms_kmeans_update': (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p]),
   'ms_sh_coded_fwd': (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_void_p, c_void_p]),
   'ms_sh_coded_bwd': (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_int, c_int] + [c_void_p] * 3 + [POINTER(c_size_t), c_void_p]),
+  'ms_tsdf_integrate': (c_int, [c_void_p] * 3 + [c_int] * 3 + [POINTER(c_double)] + [c_double] * 3 + [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
+  'ms_tsdf_classify': (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_double] + [c_void_p] * 4),
+  'ms_tsdf_emit': (c_int, [c_void_p] * 3 + [c_int] * 3 + [POINTER(c_double), c_double, c_double] + [c_void_p] * 7),
 }
 
 

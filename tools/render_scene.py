@@ -11,6 +11,7 @@ gaussians and tile overlaps; ms per frame is the median over the views after one
 
     python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d] [--transform "x 90 0.5"]
                                            [--coverage] [--sh-codes K [--coded]]
+                                           [--mesh out.ply --voxel-size s [--bounds x0 y0 z0 x1 y1 z1]]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 --transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
@@ -22,6 +23,12 @@ many gaussians are seen by no view, by some but not all (1..K-1), and by all K v
 iterations, seed 0), renders the decoded scene beside the original from every view and adds to the JSON line the two
 sizes in bytes, the time of the compression and the PSNR between the two renders (peak 1; per view and over all views).
 With --out the quantised images are written as quantised_000.npy ....
+--mesh out.ply --voxel-size s fuses the depth of the orbit views into a TSDF volume (fusion.fuse_scene: per view
+render_gaussians + render_geometry(normals=False), whose F = 2 wide pass dominates the cost — an offline operation) and
+writes the marching-tetrahedra mesh as a binary PLY with vertex colours.  --bounds is the volume's box, by default the box
+of the gaussians' positions; a box of more than 2^27 samples at that voxel size is refused.  The JSON line gains the
+volume's dims, vertex and triangle counts, the times of fusion and extraction, and the median / min / max distance of the
+vertices from the orbit centre (for a scene that is a sphere about it, the radial error on record).
 --coded (with --sh-codes) also renders the quantised scene straight from its codebook (render_compressed: no decoded
 feature tensor) and adds the PSNR of that render against the decoded one (null when they are identical) and the median
 frame time of both, after one warm-up pass each.
@@ -106,6 +113,37 @@ def coverage_report(gaussians, cameras, config):
   return report
 
 
+def mesh_report(gaussians, cameras, config, path, voxel_size, bounds):
+  """fuse_scene over ``cameras`` + extract_mesh + save_mesh_ply: dims, counts, seconds, vertex distances from the orbit centre"""
+  from taichi_splatting_amd import TSDFVolume, fuse_scene, save_mesh_ply
+  if bounds is None:
+    low, high = gaussians.position.amin(dim=0).tolist(), gaussians.position.amax(dim=0).tolist()
+  else:
+    low, high = list(bounds[:3]), list(bounds[3:])
+  if not all(h >= l for l, h in zip(low, high)):
+    raise ValueError(f"--bounds: the upper corner {high} lies below the lower corner {low}")
+  dims = tuple(int(math.ceil((h - l) / voxel_size)) + 1 for l, h in zip(low, high))
+  volume = TSDFVolume(tuple(low), voxel_size, dims, device=gaussians.position.device)       # ValueError beyond 2^27 samples
+  torch.cuda.synchronize()
+  start = time.perf_counter()
+  fuse_scene(gaussians, cameras, config, volume)
+  torch.cuda.synchronize()
+  fuse_s = time.perf_counter() - start
+  mesh = volume.extract_mesh()
+  torch.cuda.synchronize()
+  extract_s = time.perf_counter() - start - fuse_s
+  save_mesh_ply(mesh, path)
+  centre = gaussians.position.sort(dim=0).values[gaussians.position.shape[0] // 2]
+  distance = (mesh.vertices - centre).norm(dim=1) if mesh.vertices.shape[0] else torch.zeros((1,), device=centre.device)
+  report = dict(path=str(path), dims=list(dims), voxel_size=voxel_size, vertices=int(mesh.vertices.shape[0]),
+                triangles=int(mesh.faces.shape[0]), fuse_s=round(fuse_s, 4), extract_s=round(extract_s, 4),
+                distance_from_centre=[round(float(x), 6) for x in (distance.median(), distance.min(), distance.max())])
+  print(f"mesh: {dims[0]} x {dims[1]} x {dims[2]} samples of {voxel_size}; {report['vertices']} vertices, {report['triangles']} "
+        f"triangles -> {path}; fusion of {len(cameras)} views {fuse_s:.3f} s, extraction {extract_s:.3f} s; vertex distance from the "
+        f"orbit centre median / min / max {report['distance_from_centre']}", file=sys.stderr, flush=True)
+  return report
+
+
 def timed_frames(render, cameras):
   """median ms per frame of ``render(camera)`` over ``cameras`` after one warm-up pass, and the images of the timed pass"""
   images, frame_ms = [], []
@@ -184,7 +222,18 @@ def main():
   p.add_argument('--coded', action='store_true',
                  help="with --sh-codes: also render straight from the codebook (render_compressed); PSNR against the decoded "
                       "render and both frame times")
+  p.add_argument('--mesh', default=None, metavar='out.ply',
+                 help="fuse the depth of the orbit views into a TSDF volume and write its mesh (needs --voxel-size)")
+  p.add_argument('--voxel-size', type=float, default=None, metavar='s', help="sample spacing of the --mesh volume")
+  p.add_argument('--bounds', type=float, nargs=6, default=None, metavar=('x0', 'y0', 'z0', 'x1', 'y1', 'z1'),
+                 help="box of the --mesh volume (default: the box of the gaussians' positions)")
   args = p.parse_args()
+  if (args.mesh is None) != (args.voxel_size is None) or (args.bounds is not None and args.mesh is None):
+    sys.exit("render_scene: --mesh and --voxel-size go together (--bounds is optional with them)")
+  if args.voxel_size is not None and not args.voxel_size > 0:
+    sys.exit("render_scene: --voxel-size must be positive")
+  if args.mesh is not None and args.sh_degree is not None:
+    sys.exit("render_scene: --mesh fuses the scene with every stored band: it does not combine with --sh-degree")
   if args.coded and args.sh_codes is None:
     sys.exit("render_scene: --coded needs --sh-codes")
   if args.coded and args.sh_degree is not None:
@@ -246,13 +295,19 @@ def main():
       quantised = quantised_report(gaussians, cameras, config, args.sh_codes, args.sh_degree, images, args.out, coded=args.coded)
     except ValueError as e:
       sys.exit(f"render_scene: --sh-codes: {e}")
+  mesh = None
+  if args.mesh is not None:
+    try:
+      mesh = mesh_report(gaussians, cameras, config, args.mesh, args.voxel_size, args.bounds)
+    except ValueError as e:
+      sys.exit(f"render_scene: --mesh: {e}")
   print(json.dumps(dict(
     scene=str(args.scene), n=n, sh_degree=degree, sh_active_degree=args.sh_degree, transform=args.transform, image_size=list(args.size), views=args.views, orbit_radius=round(radius, 6),
     load_s=round(load_s, 4), read_s=round(timings['read_s'], 4), upload_ms=round(timings['upload_ms'], 3),
     unpack_ms=round(timings['unpack_ms'], 3), visible=visible, overlaps=overlaps,
     frame_ms=round(statistics.median(frame_ms), 4), frame_ms_per_view=[round(ms, 4) for ms in frame_ms],
     images=str(args.out) if args.out else None, **({'coverage': coverage} if coverage is not None else {}),
-    **({'quantised': quantised} if quantised is not None else {}))), flush=True)
+    **({'quantised': quantised} if quantised is not None else {}), **({'mesh': mesh} if mesh is not None else {}))), flush=True)
 
 
 if __name__ == '__main__':
