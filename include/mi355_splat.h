@@ -1117,6 +1117,64 @@ int ms_tsdf_emit(const float* tsdf, const float* weight, const float* colour /* 
                  const int32_t* vertex_scan, const int32_t* triangle_scan, float* out_vertices, int32_t* out_faces,
                  float* out_colours /* may be NULL */, void* stream);
 
+/* ---- Mesh clean-up: connected components, face selection, vertex normals (csrc/mesh.hip; an addition) -----------------
+ * A mesh is vertices (V, 3) float32 and faces (T, 3) int32, contiguous; 0 <= V <= MS_MESH_MAX_VERTICES and
+ * 0 <= 3 T <= MS_MESH_MAX_CORNERS (MS_ERR_BAD_ARG before any launch otherwise).  T = 0, V = 0, degenerate faces (a == b),
+ * duplicate faces and vertices no face references are all legal.  Faces are connected through shared vertex indices only.
+ * No call allocates, synchronises or reads device memory on the host; two runs of any call give bitwise-equal outputs.
+ * Every `tmp` follows the convention of ms_exclusive_scan_i32 (tmp == NULL: *tmp_bytes receives the size) and must be
+ * aligned to 256 bytes.
+ *
+ * LABEL RULE (ms_mesh_components).  Two vertices belong to one component iff a chain of faces links them.  Labels are
+ * dense, 0 .. K - 1, ordered by the smallest vertex index of the component; a vertex no face references gets -1, belongs
+ * to no component and is not counted; face_label[f] is the label of its corners.  The rule makes the labels independent
+ * of launch order and of any permutation of the face list.  Construction: lock-free union-find (the larger root is
+ * hooked under the smaller with a compare-and-swap, retried from the returned parent; every loop is bounded: walks by V,
+ * retries by a fixed cap), a flatten pass, one exclusive scan of the root flags, labels by gather.  head (2 int32 on the
+ * DEVICE, for the caller's one host read) receives (K, status): status is 0 or a sum of MS_MESH_BAD_INDEX (a face index
+ * outside 0 .. V - 1: found on the device, nothing is read or written through it; its face_label is -1) and
+ * MS_MESH_GAVE_UP (a lane exhausted its retries: the labels are not to be used).  head is poisoned to (-1, -1) first.
+ * ms_mesh_component_counts: vertex_count and face_count (K,) int32, zero-filled by the call; equal labels are combined
+ * inside a wave before one integer add.
+ * ms_mesh_component_filter: face_mask[f] (uint8 0 / 1) = the component of f has face_count >= min_faces (>= 1) and, when
+ * keep_largest > 0, is among the keep_largest largest of those by face count, a tie going to the lower label
+ * (keep_largest == 0: no such limit).  A face with label -1 is dropped.
+ *
+ * SELECTION ORDER (ms_mesh_select_plan / ms_mesh_select_gather).  The faces with face_mask != 0 are kept, in input order;
+ * the vertices a kept face references are kept, in input order (stable); a kept row of vertices, colours or normals is
+ * the input row bit for bit; indices are remapped.  plan: vertex_scan (V + 1) and face_scan (T + 1) int32 = exclusive
+ * scans of the keep flags, head (3 int32, device) = (V', T', status) with MS_MESH_BAD_INDEX when a KEPT face holds an
+ * index outside 0 .. V - 1 (the caller must then not gather).  The caller sizes the outputs from head: the one host read.
+ *
+ * NORMAL FORMULA (ms_mesh_vertex_normals).  s(v) = sum over the corners (f, k) with faces[f][k] == v, in ascending corner
+ * index 3 f + k, of (b - a) x (c - a) with (a, b, c) the positions of face f: the area-weighted normal, oriented as the
+ * faces are (outward for ms_tsdf_emit).  Differences, products and the running sum are FLOAT64 operations on the float32
+ * positions, in that order, without FMA contraction; out_sums (V, 3) is s rounded to float32 once, out_normals (V, 3) is
+ * s / |s| (float64 division by the float64 length) rounded to float32 once; either may be NULL.  A vertex with |s| = 0
+ * (or not finite), or that no face references, gets the normal (0, 0, 0), never a NaN.  A face with an index outside
+ * 0 .. V - 1 contributes nothing (this call reports no status: it has no host read and captures into a graph).  No float
+ * atomics: the incidence comes from a stable ms_radix_sort_pairs of the 3 T (vertex, corner) pairs and ms_find_ranges. */
+#define MS_MESH_MAX_VERTICES 2147483647
+#define MS_MESH_MAX_CORNERS 2147483647
+#define MS_MESH_BAD_INDEX 1
+#define MS_MESH_GAVE_UP 2
+int ms_mesh_components(const int32_t* faces, int64_t num_vertices, int64_t num_faces, int32_t* vertex_label,
+                       int32_t* face_label, int32_t* head, void* tmp, size_t* tmp_bytes, void* stream);
+int ms_mesh_component_counts(const int32_t* vertex_label, int64_t num_vertices, const int32_t* face_label, int64_t num_faces,
+                             int64_t num_components, int32_t* vertex_count, int32_t* face_count, void* stream);
+int ms_mesh_component_filter(const int32_t* face_count, int64_t num_components, int64_t min_faces, int64_t keep_largest,
+                             const int32_t* face_label, int64_t num_faces, uint8_t* face_mask, void* tmp, size_t* tmp_bytes,
+                             void* stream);
+int ms_mesh_select_plan(const int32_t* faces, const uint8_t* face_mask, int64_t num_vertices, int64_t num_faces,
+                        int32_t* vertex_scan, int32_t* face_scan, int32_t* head, void* tmp, size_t* tmp_bytes, void* stream);
+int ms_mesh_select_gather(const float* vertices, const float* colours /* may be NULL */, const float* normals /* may be NULL */,
+                          const int32_t* faces, const uint8_t* face_mask, int64_t num_vertices, int64_t num_faces,
+                          const int32_t* vertex_scan, const int32_t* face_scan, float* out_vertices, float* out_colours,
+                          float* out_normals, int32_t* out_faces, void* stream);
+int ms_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t num_vertices, int64_t num_faces,
+                           float* out_sums /* may be NULL */, float* out_normals /* may be NULL */, void* tmp,
+                           size_t* tmp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

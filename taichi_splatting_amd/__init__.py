@@ -29,6 +29,8 @@ from .spherical_harmonics import evaluate_sh_coded, make_coded_sh_plan, CodedSHP
 from .appearance import apply_bilateral_grid, BilateralGrids, identity_bilateral_grid, bilateral_grid_tv
 from .geometry import gaussian_normals, render_geometry, GeometryImages, normal_consistency_loss, normal_consistency
 from .fusion import TSDFVolume, TriangleMesh, save_mesh_ply, fuse_scene
+from .mesh import (MeshComponents, mesh_components, select_faces, remove_small_components, vertex_normals,
+                   vertex_normal_sums, with_vertex_normals)
 
 __version__ = '0.5.1'       # = MS_VERSION 501 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -49,6 +51,8 @@ __all__ = [
   'apply_bilateral_grid', 'BilateralGrids', 'identity_bilateral_grid', 'bilateral_grid_tv',
   'gaussian_normals', 'render_geometry', 'GeometryImages', 'normal_consistency_loss', 'normal_consistency',
   'TSDFVolume', 'TriangleMesh', 'save_mesh_ply', 'fuse_scene',
+  'MeshComponents', 'mesh_components', 'select_faces', 'remove_small_components', 'vertex_normals', 'vertex_normal_sums',
+  'with_vertex_normals',
 ]
 
 
@@ -61,7 +65,7 @@ def install_as_taichi_splatting():
   for sub in ('data_types', 'scene_io', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
-              'rasterizer.function', 'rasterizer.wide', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'geometry', 'fusion', 'optim', 'optim.fractional', 'optim.relocate',
+              'rasterizer.function', 'rasterizer.wide', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'geometry', 'fusion', 'mesh', 'optim', 'optim.fractional', 'optim.relocate',
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',

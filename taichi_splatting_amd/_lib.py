@@ -40,6 +40,8 @@ SH_CODED_CHUNK = 512            # MS_SH_CODED_CHUNK: entries of the code order p
 TSDF_MAX_SAMPLES = 1 << 27        # MS_TSDF_MAX_SAMPLES: nx ny nz of a TSDF volume
 TSDF_RUN = 4                      # MS_TSDF_RUN: consecutive samples a lane of ms_tsdf_integrate owns
 TSDF_CAMERA_CHUNK = 64            # MS_TSDF_CAMERA_CHUNK: cameras a wave of ms_tsdf_integrate culls per ballot
+MESH_MAX_VERTICES = MESH_MAX_CORNERS = 2 ** 31 - 1   # MS_MESH_MAX_VERTICES / MS_MESH_MAX_CORNERS
+MESH_BAD_INDEX, MESH_GAVE_UP = 1, 2               # MS_MESH_BAD_INDEX / MS_MESH_GAVE_UP (status bits of the mesh calls)
 RELOCATE_COPY, RELOCATE_ZERO_TOUCHED, RELOCATE_INHERIT, RELOCATE_OPACITY, RELOCATE_SCALE = range(5)   # MS_RELOCATE_*
 
 _lib: Optional[ctypes.CDLL] = None
@@ -236,6 +238,12 @@ SIGNATURES = {
   'ms_tsdf_integrate': (c_int, [c_void_p] * 3 + [c_int] * 3 + [POINTER(c_double)] + [c_double] * 3 + [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
   'ms_tsdf_classify': (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_double] + [c_void_p] * 4),
   'ms_tsdf_emit': (c_int, [c_void_p] * 3 + [c_int] * 3 + [POINTER(c_double), c_double, c_double] + [c_void_p] * 7),
+  'ms_mesh_components': (c_int, [c_void_p, c_int64, c_int64] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p]),
+  'ms_mesh_component_counts': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64] + [c_void_p] * 3),
+  'ms_mesh_component_filter': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
+  'ms_mesh_select_plan': (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p]),
+  'ms_mesh_select_gather': (c_int, [c_void_p] * 5 + [c_int64, c_int64] + [c_void_p] * 7),
+  'ms_mesh_vertex_normals': (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 3 + [POINTER(c_size_t), c_void_p]),
 }
 
 

@@ -2,15 +2,15 @@
 ``ms_tsdf_integrate`` for all frames of a call) and triangulate it (``TSDFVolume.extract_mesh``: marching tetrahedra,
 classify -> two scans -> emit), ``csrc/tsdf.hip``.  ``fuse_scene`` renders the depth of a camera set and fuses it;
 ``save_mesh_ply`` writes the mesh.  The reference has no counterpart: this is the step 2DGS, GOF and PGSR take from
-rendered depth to a surface.
+rendered depth to a surface.  ``mesh.py`` cleans the mesh (components, small-part removal) and gives it vertex normals.
 
 float32 only, detached, no autograd; there is no torch fallback and CPU tensors raise, as everywhere in this package.
 ``integrate`` allocates nothing, never synchronises and never reads back: it captures into a graph.  ``extract_mesh``
 reads the two scan totals on the host once, to size its outputs, and therefore does not capture.  No kernel uses an
 atomic: both calls are bitwise reproducible.
 
-Out of scope: sparse or hashed volumes, float64, gradients, median depth, vertex normals, mesh simplification or
-cleaning, marching cubes, tile-row strips and more than one GPU.
+Out of scope: sparse or hashed volumes, float64, gradients, median depth, mesh simplification, marching cubes,
+tile-row strips and more than one GPU.
 """
 from __future__ import annotations
 
@@ -50,10 +50,12 @@ def _f32(x, name: str) -> float:
 @dataclass
 class TriangleMesh:
   """``vertices`` (V, 3) float32, ``faces`` (T, 3) int32 (indices into ``vertices``; ``(b - a) x (c - a)`` points to the
-  positive, outside, side of the field), ``colours`` (V, 3) float32 or None.  Ordered as ``TSDFVolume.extract_mesh`` states."""
+  positive, outside, side of the field), ``colours`` (V, 3) float32 or None, ``normals`` (V, 3) float32 or None (filled by
+  ``mesh.with_vertex_normals``).  Ordered as ``TSDFVolume.extract_mesh`` states."""
   vertices: torch.Tensor
   faces: torch.Tensor
   colours: Optional[torch.Tensor] = None
+  normals: Optional[torch.Tensor] = None
 
 
 class TSDFVolume:
@@ -272,9 +274,9 @@ class TSDFVolume:
 
 
 def save_mesh_ply(mesh: TriangleMesh, path) -> None:
-  """Write ``mesh`` as a binary little-endian PLY: element ``vertex`` with float ``x y z`` (+ uchar ``red green blue``,
-  ``round(255 clamp(colour, 0, 1))``, when the mesh has colours), element ``face`` with ``list uchar int
-  vertex_indices``.  Tensors on any device."""
+  """Write ``mesh`` as a binary little-endian PLY: element ``vertex`` with float ``x y z`` (+ float ``nx ny nz`` when the
+  mesh has normals, + uchar ``red green blue``, ``round(255 clamp(colour, 0, 1))``, when it has colours, in that order),
+  element ``face`` with ``list uchar int vertex_indices``.  Tensors on any device."""
   if not isinstance(mesh, TriangleMesh):
     raise TypeError(f"save_mesh_ply expects a TriangleMesh (got {type(mesh).__name__})")
   vertices = mesh.vertices.detach().cpu()
@@ -288,6 +290,12 @@ def save_mesh_ply(mesh: TriangleMesh, path) -> None:
     raise ValueError(f"a face refers to a vertex outside 0..{count - 1}")
   coloured = mesh.colours is not None
   fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+  shaded = mesh.normals is not None
+  if shaded:
+    normals = mesh.normals.detach().cpu()
+    if tuple(normals.shape) != (count, 3) or not normals.dtype.is_floating_point:
+      raise ValueError(f"normals must be float (V, 3) = ({count}, 3) (got {normals.dtype} {tuple(normals.shape)})")
+    fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
   if coloured:
     colours = mesh.colours.detach().cpu()
     if tuple(colours.shape) != (count, 3):
@@ -297,6 +305,10 @@ def save_mesh_ply(mesh: TriangleMesh, path) -> None:
   xyz = vertices.to(torch.float32).numpy()
   for a, name in enumerate('xyz'):
     vertex_rows[name] = xyz[:, a]
+  if shaded:
+    nxyz = normals.to(torch.float32).numpy()
+    for a, name in enumerate(('nx', 'ny', 'nz')):
+      vertex_rows[name] = nxyz[:, a]
   if coloured:
     rgb = torch.nan_to_num(colours.to(torch.float32), nan=0.0).clamp(0.0, 1.0).mul(255.0).round().to(torch.uint8).numpy()
     for a, name in enumerate(('red', 'green', 'blue')):
@@ -306,6 +318,8 @@ def save_mesh_ply(mesh: TriangleMesh, path) -> None:
   face_rows['v'] = faces.to(torch.int32).numpy()
   header = ["ply", "format binary_little_endian 1.0", f"element vertex {count}",
             "property float x", "property float y", "property float z"]
+  if shaded:
+    header += ["property float nx", "property float ny", "property float nz"]
   if coloured:
     header += ["property uchar red", "property uchar green", "property uchar blue"]
   header += [f"element face {faces.shape[0]}", "property list uchar int vertex_indices", "end_header"]

@@ -11,7 +11,8 @@ gaussians and tile overlaps; ms per frame is the median over the views after one
 
     python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d] [--transform "x 90 0.5"]
                                            [--coverage] [--sh-codes K [--coded]]
-                                           [--mesh out.ply --voxel-size s [--bounds x0 y0 z0 x1 y1 z1]]
+                                           [--mesh out.ply --voxel-size s [--bounds x0 y0 z0 x1 y1 z1]
+                                            [--min-component-faces N] [--keep-components K] [--mesh-normals]]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 --transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
@@ -29,6 +30,10 @@ writes the marching-tetrahedra mesh as a binary PLY with vertex colours.  --boun
 of the gaussians' positions; a box of more than 2^27 samples at that voxel size is refused.  The JSON line gains the
 volume's dims, vertex and triangle counts, the times of fusion and extraction, and the median / min / max distance of the
 vertices from the orbit centre (for a scene that is a sphere about it, the radial error on record).
+--min-component-faces N (default 1: nothing removed) drops the connected components of the mesh with fewer than N
+triangles and --keep-components K (default: all) keeps only the K largest (mesh.remove_small_components, on the device);
+--mesh-normals adds area-weighted vertex normals (nx ny nz) to the written file.  With either of the first two the JSON
+line also gains the counts before cleaning, the number of components found and the time of the clean-up.
 --coded (with --sh-codes) also renders the quantised scene straight from its codebook (render_compressed: no decoded
 feature tensor) and adds the PSNR of that render against the decoded one (null when they are identical) and the median
 frame time of both, after one warm-up pass each.
@@ -113,7 +118,8 @@ def coverage_report(gaussians, cameras, config):
   return report
 
 
-def mesh_report(gaussians, cameras, config, path, voxel_size, bounds):
+def mesh_report(gaussians, cameras, config, path, voxel_size, bounds, min_component_faces=1, keep_components=None,
+                mesh_normals=False):
   """fuse_scene over ``cameras`` + extract_mesh + save_mesh_ply: dims, counts, seconds, vertex distances from the orbit centre"""
   from taichi_splatting_amd import TSDFVolume, fuse_scene, save_mesh_ply
   if bounds is None:
@@ -132,12 +138,29 @@ def mesh_report(gaussians, cameras, config, path, voxel_size, bounds):
   mesh = volume.extract_mesh()
   torch.cuda.synchronize()
   extract_s = time.perf_counter() - start - fuse_s
+  cleaning = None
+  if min_component_faces > 1 or keep_components is not None:
+    from taichi_splatting_amd import remove_small_components
+    before = (int(mesh.vertices.shape[0]), int(mesh.faces.shape[0]))
+    clean_start = time.perf_counter()
+    mesh, components = remove_small_components(mesh, min_faces=min_component_faces, keep_largest=keep_components,
+                                               return_components=True)
+    torch.cuda.synchronize()
+    cleaning = dict(vertices_before=before[0], triangles_before=before[1], components=components.num_components,
+                    clean_s=round(time.perf_counter() - clean_start, 4))
+  if mesh_normals:
+    from taichi_splatting_amd import with_vertex_normals
+    mesh = with_vertex_normals(mesh)
   save_mesh_ply(mesh, path)
   centre = gaussians.position.sort(dim=0).values[gaussians.position.shape[0] // 2]
   distance = (mesh.vertices - centre).norm(dim=1) if mesh.vertices.shape[0] else torch.zeros((1,), device=centre.device)
   report = dict(path=str(path), dims=list(dims), voxel_size=voxel_size, vertices=int(mesh.vertices.shape[0]),
                 triangles=int(mesh.faces.shape[0]), fuse_s=round(fuse_s, 4), extract_s=round(extract_s, 4),
                 distance_from_centre=[round(float(x), 6) for x in (distance.median(), distance.min(), distance.max())])
+  if cleaning is not None:
+    report.update(cleaning)
+  if mesh_normals:
+    report['normals'] = True
   print(f"mesh: {dims[0]} x {dims[1]} x {dims[2]} samples of {voxel_size}; {report['vertices']} vertices, {report['triangles']} "
         f"triangles -> {path}; fusion of {len(cameras)} views {fuse_s:.3f} s, extraction {extract_s:.3f} s; vertex distance from the "
         f"orbit centre median / min / max {report['distance_from_centre']}", file=sys.stderr, flush=True)
@@ -225,11 +248,20 @@ def main():
   p.add_argument('--mesh', default=None, metavar='out.ply',
                  help="fuse the depth of the orbit views into a TSDF volume and write its mesh (needs --voxel-size)")
   p.add_argument('--voxel-size', type=float, default=None, metavar='s', help="sample spacing of the --mesh volume")
+  p.add_argument('--min-component-faces', type=int, default=1, metavar='N',
+                 help="drop the connected components of the --mesh mesh with fewer than N triangles (default 1: none)")
+  p.add_argument('--keep-components', type=int, default=None, metavar='K',
+                 help="keep only the K largest components of the --mesh mesh (default: all)")
+  p.add_argument('--mesh-normals', action='store_true', help="write area-weighted vertex normals into the --mesh file")
   p.add_argument('--bounds', type=float, nargs=6, default=None, metavar=('x0', 'y0', 'z0', 'x1', 'y1', 'z1'),
                  help="box of the --mesh volume (default: the box of the gaussians' positions)")
   args = p.parse_args()
   if (args.mesh is None) != (args.voxel_size is None) or (args.bounds is not None and args.mesh is None):
     sys.exit("render_scene: --mesh and --voxel-size go together (--bounds is optional with them)")
+  if args.mesh is None and (args.min_component_faces != 1 or args.keep_components is not None or args.mesh_normals):
+    sys.exit("render_scene: --min-component-faces, --keep-components and --mesh-normals need --mesh")
+  if args.min_component_faces < 1 or (args.keep_components is not None and args.keep_components < 1):
+    sys.exit("render_scene: --min-component-faces and --keep-components must be at least 1")
   if args.voxel_size is not None and not args.voxel_size > 0:
     sys.exit("render_scene: --voxel-size must be positive")
   if args.mesh is not None and args.sh_degree is not None:
@@ -298,7 +330,8 @@ def main():
   mesh = None
   if args.mesh is not None:
     try:
-      mesh = mesh_report(gaussians, cameras, config, args.mesh, args.voxel_size, args.bounds)
+      mesh = mesh_report(gaussians, cameras, config, args.mesh, args.voxel_size, args.bounds, args.min_component_faces,
+                         args.keep_components, args.mesh_normals)
     except ValueError as e:
       sys.exit(f"render_scene: --mesh: {e}")
   print(json.dumps(dict(
