@@ -6,9 +6,18 @@
  *     MS_ERR_* code on an argument error; ms_last_error_string() describes the last failure.
  *   - all pointers are DEVICE pointers unless the name ends in _host; tensors are contiguous,
  *     row-major; image_size is (W, H), images are (H, W, C).
- *   - no function allocates device memory or synchronises (callers own every buffer, including
- *     scratch: functions taking (tmp, tmp_bytes) report the required size in *tmp_bytes when
- *     tmp == NULL and do nothing else).
+ *   - no function allocates device memory or synchronises: callers own every buffer, scratch included.
+ *   - scratch blocks, (tmp, tmp_bytes) — one convention for every function with that pair (ms_map_tiles_direct names
+ *     it (scratch, scratch_bytes)): called with tmp == NULL the function stores the size the block must have for these
+ *     sizes in *tmp_bytes, returns 0 and does nothing else — data pointers may be NULL, no stream is touched.  The size
+ *     is a multiple of 256 bytes, depends on the size arguments alone, and may be 0.  Called with a block, *tmp_bytes is
+ *     the block's size (read, never written) and the function carves its arrays from the block at offsets that are
+ *     multiples of 256 bytes: a block aligned to 256 bytes gives every array that alignment (the ms_mesh_* functions
+ *     require it of tmp and return MS_ERR_BAD_ARG otherwise; ms_map_tiles_direct requires 16 bytes; the rest take any
+ *     address hipMalloc or a tensor allocator returns).  Errors, checked after the size arguments and before the data
+ *     pointers: tmp_bytes == NULL is MS_ERR_BAD_ARG; a block smaller than the reported size is MS_ERR_TMP_TOO_SMALL
+ *     with the message "<function>: tmp_bytes too small (<given> < <needed>)", and nothing is launched.  One exception,
+ *     kept for its callers: ms_knn_points returns MS_ERR_BAD_ARG, with the same message, for a block that is too small.
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*; NULL = default stream).
  *   - dtype selects the float (MS_F32) or double (MS_F64) instantiation, the way the reference
  *     specialises its Taichi kernels on the tensor dtype (rasterizer/function.py:126).
@@ -160,13 +169,13 @@ int ms_depth_sort_keys(const void* depth, int64_t v, int depth16, double ndc_nea
 /* ms_depth_sort_keys + ms_radix_sort_pairs (32 bit keys, all 32 or 16 bits) in one call: the first radix pass makes
  * its keys from `depth` on the fly and takes the item index as value, so no key / value arrays exist before the
  * first scatter.  out_order[j] = index of the j-th gaussian in (depth, index) order, out_sorted_keys its key.
- * tmp: call with tmp == NULL for *tmp_bytes (same size as ms_radix_sort_pairs for v 4-byte keys). */
+ * (tmp, tmp_bytes): see Conventions; the size ms_radix_sort_pairs reports for v 4-byte keys. */
 int ms_depth_argsort(const void* depth, int64_t v, int depth16, double ndc_near, double ndc_far, int dtype,
                      uint32_t* out_sorted_keys, int32_t* out_order, void* tmp, size_t* tmp_bytes, void* stream);
 
 /* cuda_lib.full_cumsum (cuda_lib/full_cumsum.cu:17-67): exclusive scan of n int32 into out[0..n],
  * out[n] = total.  If total_host is not NULL it must be pinned, device-visible host memory and
- * receives the total as well (valid after the stream is synchronised). */
+ * receives the total as well (valid after the stream is synchronised).  (tmp, tmp_bytes): see Conventions. */
 int ms_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* total_host,
                           void* tmp, size_t* tmp_bytes, void* stream);
 
@@ -184,7 +193,7 @@ int ms_tile_emit(const float* points7, const float* depth, const int32_t* order,
 
 /* cuda_lib.radix_sort_pairs (cuda_lib/radix_sort_pairs.cu:8-70 = cub::DeviceRadixSort::SortPairs):
  * stable LSD radix sort of n (key, int32 value) pairs on key bits [begin_bit, end_bit),
- * out-of-place, inputs preserved.  key_bytes is 4 or 8 (unsigned order). */
+ * out-of-place, inputs preserved.  key_bytes is 4 or 8 (unsigned order).  (tmp, tmp_bytes): see Conventions. */
 int ms_radix_sort_pairs(const void* keys_in, const int32_t* values_in, void* keys_out,
                         int32_t* values_out, int64_t n, int key_bytes, int begin_bit, int end_bit,
                         void* tmp, size_t* tmp_bytes, void* stream);
@@ -227,7 +236,7 @@ int ms_tile_payload_sort(const int32_t* tile_ranges, int64_t num_tiles, uint64_t
  * count is zero emits nothing); image_w / image_h padded to the tile size.  k_capacity: entries of
  * out_overlap_to_point.  out_tile_ranges (tiles, 2), written whole.  out_counters: 8 int32 on the device —
  * [0] = K = cum[v], [1] = K when K <= k_capacity, else 0, [2] = 1 on that overflow (nothing is emitted, every range is
- * [0, 0)), the rest internal.  Scratch query: scratch == NULL -> *scratch_bytes. */
+ * [0, 0)), the rest internal.  (scratch, scratch_bytes): the (tmp, tmp_bytes) of Conventions; 16-byte aligned. */
 int ms_map_tiles_direct(const float* points7, const void* depth, int depth_dtype, const int32_t* cum, int64_t v,
                         int image_w, int image_h, int tile_size, float alpha_threshold, int tile_row_begin,
                         int tile_row_end, int depth16, double ndc_near, double ndc_far, int64_t k_capacity,
@@ -637,9 +646,9 @@ int ms_morton_codes64(const float* points3, int64_t n, const float* lower3_host,
  * which permutation, only the speed does (an entry outside 0..N-1 is clamped: wrong results, no stray access).
  * out_stats: NULL, or a device int64[2] to which the search ADDS [blocks scanned x queries of the wave, point-query
  * distance evaluations] (the caller zeroes it); brute force would evaluate N (N - 1).
- * tmp: call with tmp == NULL for *tmp_bytes.  No host read, allocation or synchronisation: capturable into a graph.
+ * (tmp, tmp_bytes): see Conventions.  No host read, allocation or synchronisation: capturable into a graph.
  * MS_ERR_BAD_ARG names the argument: n < 0, n >= 2^31, k, null points3 / order / out_dist2 with n > 0, null tmp_bytes,
- * *tmp_bytes too small.  n == 0 returns 0 without a launch. */
+ * and — this function only — a *tmp_bytes that is too small.  n == 0 returns 0 without a launch. */
 #define MS_KNN_BLOCK 256
 int ms_knn_points(const float* points3, const int32_t* order, int64_t n, int k,
                   float* out_dist2, int32_t* out_index /* may be NULL */, int64_t* out_stats /* may be NULL */,
@@ -723,8 +732,8 @@ int ms_strip_return_rows(const float* back_rows, const int64_t* send_index, cons
  * ms_densify_plan: prune / split are n bytes each (non-zero = set).  scan (2 n + 1 int32) receives the exclusive scan
  * of [keep flags | split flags] (scan[i] = destination of kept row i, scan[n] = n_kept, scan[n + i] - n_kept = rank of
  * split parent i).  counts (device, 4 int32) = (n_kept, n_split_parents, n_out, n); counts_host (pinned, device-visible
- * host memory, may be NULL) receives the same, valid after the stream is synchronised.  (tmp, tmp_bytes) as for
- * ms_exclusive_scan_i32.  n * children and 2 n + 1 must fit int32.
+ * host memory, may be NULL) receives the same, valid after the stream is synchronised.  (tmp, tmp_bytes): see
+ * Conventions.  n * children and 2 n + 1 must fit int32.
  * ms_densify_table: the source table over the n_out destination rows: src_row (source row) and child_slot
  * (0 .. children - 1 for a child, -1 for a kept row). */
 int ms_densify_plan(const uint8_t* prune, const uint8_t* split, int64_t n, int children, int32_t* scan,
@@ -781,7 +790,7 @@ int ms_densify_split3d(float* position, float* log_scaling, const float* rotatio
  * all three NULL, or three arrays of the ssim map's shape that receive, per element, what the backward needs:
  * A = d ssim/d mu1 - 2 mu1 B - mu2 C,  B = d ssim/d s11,  C = d ssim/d s12.  tmp holds one pair of partial sums
  * (double) per workgroup, added in a fixed order by a second kernel: the result is bit-reproducible (no atomics).
- * tmp == NULL: *tmp_bytes receives the size tmp must have and nothing is launched.
+ * (tmp, tmp_bytes): see Conventions.
  * ms_photometric_bwd: grad_image (H, W, C) =
  *   grad_out * [ (1 - lambda) / (H W C) sign(x - y) - lambda / (map elements) (G*A + 2 x G*B + y G*C) ],
  * sign(0) = 0; the maps are those of a forward with the same sizes and padding (`valid`: absent map elements count as
@@ -817,8 +826,8 @@ int ms_photometric_bwd(const void* image, const void* target, const void* map_a,
  *       differentiated as grid_sample does, and is flat where it is clamped
  * grad_image NULL or grad_grid NULL skips that gradient (and its kernels).  grad_grid is a gather without atomics: a
  * workgroup sums one vertex's weights over a chunk of its footprint into tmp (double), a second kernel adds the chunks
- * in a fixed order: bit-reproducible.  tmp == NULL: *tmp_bytes receives the size tmp must have for these sizes (the
- * same whichever gradients are asked for) and nothing is launched.  Neither call reads back to the host.
+ * in a fixed order: bit-reproducible.  (tmp, tmp_bytes): see Conventions (the size is the same whichever gradients
+ * are asked for).  Neither call reads back to the host.
  * 1 <= L <= 16, 1 <= Gy, Gx <= 128, H W 3 < 2^31.
  * MS_ERR_BAD_ARG: null pointer, a size <= 0, both gradients NULL; MS_ERR_UNSUPPORTED: unknown dtype, sizes beyond the
  * limits; MS_ERR_TMP_TOO_SMALL. */
@@ -848,8 +857,8 @@ int ms_bilagrid_bwd(const void* image, const void* grid, const void* grad_out, i
  * w = pixel_weight (H, W), or alpha where pixel_weight is NULL, where the pixel and its four neighbours all have
  * alpha >= alpha_min (> 0 required; d is evaluated nowhere else), and 0 elsewhere.  H < 3 or W < 3: exactly 0.
  * depth_normals: NULL or (H, W, 3), receives n_d (0 outside the interior and where w's indicator fails).  tmp holds one
- * double per workgroup, added in a fixed order by a second kernel: bit-reproducible.  tmp == NULL: *tmp_bytes receives the
- * size tmp must have and nothing is launched.
+ * double per workgroup, added in a fixed order by a second kernel: bit-reproducible.  (tmp, tmp_bytes): see
+ * Conventions.
  * ms_normal_consistency_bwd: ONE launch; grad_accum (H, W, F) = grad_loss * d out_loss / d accum in the depth, alpha and
  * normal channels, exactly 0 in every other channel; every element is written.  w is a constant, a vector under
  * MS_NORMAL_TINY a constant 0, and there is no gradient for projection.  grad_loss is ONE value of `dtype` in DEVICE
@@ -1003,9 +1012,9 @@ int ms_perturb_positions(float* position, const float* log_scaling, const float*
                          const float* z, int64_t n, float step, double k, double x0, void* stream);
 
 /* ---- k-means over (N, D) float32 rows: the two halves of a Lloyd iteration (no reference counterpart) ----
- * 1 <= d <= MS_KMEANS_MAX_D, 1 <= k <= MS_KMEANS_MAX_K, 0 <= n < 2^31 - 1024.  Both calls: tmp == NULL returns
- * *tmp_bytes for (n, d, k); no host read, allocation, synchronisation or atomic, so they capture into a graph and two
- * runs are bitwise equal.  MS_ERR_BAD_ARG names the argument; MS_ERR_TMP_TOO_SMALL a short *tmp_bytes.
+ * 1 <= d <= MS_KMEANS_MAX_D, 1 <= k <= MS_KMEANS_MAX_K, 0 <= n < 2^31 - 1024.  Both calls: (tmp, tmp_bytes) as in
+ * Conventions, sized by (n, d, k); no host read, allocation, synchronisation or atomic, so they capture into a graph and two
+ * runs are bitwise equal.  MS_ERR_BAD_ARG names the argument.
  *
  * ms_kmeans_assign: out_index[i] = argmin_j s(i, j), s(i, j) = ||c_j||^2 - 2 x_i . c_j evaluated on the exact
  * f32-input MFMA as the fmaf chain that starts at ||c_j||^2 (a float64 sum rounded once) and adds -2 x_ik c_jk for
@@ -1049,8 +1058,8 @@ int ms_kmeans_update(const float* x, const int32_t* index, const float* weights 
  * storage-order pass writes (g, dir) of every gaussian into its place of the list, a workgroup sums the products
  * (double)g (double)Y of one chunk, a wave adds the chunks of one code in list order and rounds to float32 once: two
  * runs are bitwise equal.  Entries of the plan are clamped to their ranges.  With g_codebook == NULL only out and g_out
- * are read.  tmp == NULL returns *tmp_bytes for (n, num_chunks, sh_degree): the chunk sums and 24 bytes per gaussian.
- * MS_ERR_BAD_ARG names the argument. */
+ * are read.  (tmp, tmp_bytes) as in Conventions, sized by (n, num_chunks, sh_degree): the chunk sums and 24 bytes per
+ * gaussian.  MS_ERR_BAD_ARG names the argument. */
 #define MS_SH_CODED_CHUNK 512
 int ms_sh_coded_fwd(const float* dc, const int32_t* index, const float* codebook, const float* positions,
                     const float* cam_pos, int64_t n, int k, int sh_degree, float* out, void* stream);
@@ -1122,8 +1131,7 @@ int ms_tsdf_emit(const float* tsdf, const float* weight, const float* colour /* 
  * 0 <= 3 T <= MS_MESH_MAX_CORNERS (MS_ERR_BAD_ARG before any launch otherwise).  T = 0, V = 0, degenerate faces (a == b),
  * duplicate faces and vertices no face references are all legal.  Faces are connected through shared vertex indices only.
  * No call allocates, synchronises or reads device memory on the host; two runs of any call give bitwise-equal outputs.
- * Every `tmp` follows the convention of ms_exclusive_scan_i32 (tmp == NULL: *tmp_bytes receives the size) and must be
- * aligned to 256 bytes.
+ * Every (tmp, tmp_bytes) follows Conventions, and tmp must be aligned to 256 bytes (MS_ERR_BAD_ARG otherwise).
  *
  * LABEL RULE (ms_mesh_components).  Two vertices belong to one component iff a chain of faces links them.  Labels are
  * dense, 0 .. K - 1, ordered by the smallest vertex index of the component; a vertex no face references gets -1, belongs

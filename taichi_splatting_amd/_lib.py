@@ -317,6 +317,39 @@ def current_stream(device) -> int:
   return torch.cuda.current_stream(device).cuda_stream
 
 
+# ---- scratch blocks: the (tmp, tmp_bytes) convention of include/mi355_splat.h.  ``call(tmp_ptr, size_ref)`` is the entry
+# point with every other argument bound; these three are the only code that speaks the protocol.
+
+def scratch_bytes(call, what: str) -> int:
+  """Bytes of scratch ``call`` needs: the size query (a NULL block)."""
+  need = c_size_t(0)
+  check(call(None, ctypes.byref(need)), what)
+  return need.value
+
+
+def run_in_scratch(call, scratch: torch.Tensor, what: str) -> None:
+  """Run ``call`` in a uint8 block the caller owns (the library checks its size)."""
+  check(call(ptr(scratch), ctypes.byref(c_size_t(scratch.numel()))), what)
+
+
+def scratch_block(nbytes: int, device) -> torch.Tensor:
+  """A uint8 block of ``nbytes`` (an empty block still gets an address)."""
+  return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device)
+
+
+def run_with_scratch(call, device, what: str) -> None:
+  """Query, allocate on ``device``, run."""
+  run_in_scratch(call, scratch_block(scratch_bytes(call, what), device), what)
+
+
+def exclusive_scan(values: int, n: int, out: int, device, what: str, total_host: Optional[int] = None) -> None:
+  """``ms_exclusive_scan_i32`` on the current stream of ``device``: ``out[0 .. n]`` = exclusive scan of the ``n`` int32 at
+  ``values`` (device pointers; equal for an in-place scan), ``out[n]`` = the total, which also goes to the pinned host
+  word ``total_host`` when given."""
+  lib, stream = load(), current_stream(device)
+  run_with_scratch(lambda tmp, size: lib.ms_exclusive_scan_i32(values, n, out, total_host, tmp, size, stream), device, what)
+
+
 def raster_config_c(config) -> RasterConfigC:
   return RasterConfigC(
     tile_size=config.tile_size, antialias=int(config.antialias),

@@ -10,7 +10,6 @@ gather without atomics and is bitwise reproducible.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple, Union
 
 import torch
@@ -56,15 +55,11 @@ def bilagrid_backward(image: torch.Tensor, grid: torch.Tensor, grad_out: torch.T
   h, w, _ = image.shape
   _, l, gy, gx = grid.shape
   dtype, stream = _lib.dtype_code(image.dtype), _lib.current_stream(image.device)
-  need = ctypes.c_size_t(0)
-  _lib.check(lib.ms_bilagrid_bwd(None, None, None, h, w, l, gy, gx, dtype, None, None, None, ctypes.byref(need), stream),
-             "apply_bilateral_grid backward")
-  tmp = torch.empty((need.value,), dtype=torch.uint8, device=image.device)
   grad_image = torch.empty_like(image) if want_image else None
   grad_grid = torch.empty_like(grid) if want_grid else None       # written whole by the kernels
-  _lib.check(lib.ms_bilagrid_bwd(_lib.ptr(image), _lib.ptr(grid), _lib.ptr(grad_out), h, w, l, gy, gx, dtype,
-                                 _lib.ptr(grad_image), _lib.ptr(grad_grid), tmp.data_ptr(), ctypes.byref(need), stream),
-             "apply_bilateral_grid backward")
+  _lib.run_with_scratch(lambda tmp, size: lib.ms_bilagrid_bwd(
+    _lib.ptr(image), _lib.ptr(grid), _lib.ptr(grad_out), h, w, l, gy, gx, dtype, _lib.ptr(grad_image), _lib.ptr(grad_grid),
+    tmp, size, stream), image.device, "apply_bilateral_grid backward")
   return grad_image, grad_grid
 
 

@@ -455,14 +455,8 @@ extern "C" int ms_bilagrid_bwd(const void* image, const void* grid, const void* 
                                void* stream) {
   const int rc = bg_check(H, W, L, Gy, Gx, dtype, "ms_bilagrid_bwd");
   if (rc) return rc;
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
   const BgChunks c = bg_chunks(H, W, Gy, Gx);
-  const size_t need = align_up((size_t)(c.x * c.y) * Gy * Gx * L * BG_K * sizeof(double), 256);
-  if (tmp == nullptr) { *tmp_bytes = need; return 0; }
-  if (*tmp_bytes < need) {
-    set_error("ms_bilagrid_bwd: tmp_bytes %zu < %zu", *tmp_bytes, need);
-    return MS_ERR_TMP_TOO_SMALL;
-  }
+  MS_CHECK_TMP(tmp, tmp_bytes, Carve::one((size_t)(c.x * c.y) * Gy * Gx * L * BG_K * sizeof(double)));
   MS_CHECK_ARG(image && grid && grad_out, "null pointer");
   MS_CHECK_ARG(grad_image || grad_grid, "grad_image and grad_grid are both null: nothing to compute");
   hipStream_t s = (hipStream_t)stream;

@@ -42,6 +42,41 @@ void set_error(const char* fmt, ...);
 static inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// ---- scratch blocks: the (tmp, tmp_bytes) convention of include/mi355_splat.h ------------------------------------
+// Every entry point with a scratch block lays it out with ONE Carve and answers the two-call protocol with ONE
+// MS_CHECK_TMP, after its shape checks and before its null-pointer checks; nothing else sizes or splits a block.
+// The carver: a running offset in units of 256 bytes.  An empty region takes no room (and shares its offset with the
+// next one); a layout that gives empty regions a place of their own passes max(bytes, 1).
+struct Carve {
+  size_t off = 0;       // bytes taken so far: the size of the block once every region is taken
+  size_t take(size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; }
+  static size_t one(size_t bytes) { return align_up(bytes, 256); }   // size of a block with a single region (at offset 0)
+};
+template <class T>
+static inline T* at(void* base, size_t off) { return (T*)((char*)base + off); }
+
+// scratch of the scan and the radix sort (scan_sort.hip), for the stages that nest them in their own block
+size_t scan_tmp_size(int64_t n);
+size_t sort_tmp_size(int64_t n, int key_bytes, bool adaptive = false);   // adaptive: depth_argsort_launch's layout
+
+// true: the entry point returns *rc now (null tmp_bytes, a size query answered, or a block that is too small)
+static inline bool tmp_answered(const char* who, const void* tmp, size_t* tmp_bytes, size_t need, int too_small, int* rc) {
+  if (tmp_bytes == nullptr) { set_error("%s: tmp_bytes is null", who); *rc = MS_ERR_BAD_ARG; return true; }
+  if (tmp == nullptr) { *tmp_bytes = need; *rc = 0; return true; }
+  if (*tmp_bytes < need) {
+    set_error("%s: tmp_bytes too small (%zu < %zu)", who, *tmp_bytes, need);
+    *rc = too_small;
+    return true;
+  }
+  return false;
+}
+#define MS_CHECK_TMP_AS(tmp, tmp_bytes, need, too_small)                                   \
+  do {                                                                                     \
+    int rc__;                                                                              \
+    if (ms::tmp_answered(__func__, tmp, tmp_bytes, need, too_small, &rc__)) return rc__;   \
+  } while (0)
+#define MS_CHECK_TMP(tmp, tmp_bytes, need) MS_CHECK_TMP_AS(tmp, tmp_bytes, need, MS_ERR_TMP_TOO_SMALL)
+
 // ---- wave64 primitives -------------------------------------------------------------------------
 constexpr int WAVE = 64;
 

@@ -217,8 +217,7 @@ extern "C" int ms_densify_plan(const uint8_t* prune, const uint8_t* split, int64
                                int32_t* counts, int32_t* counts_host, void* tmp, size_t* tmp_bytes, void* stream) {
   const int rc = check_plan_sizes(n, children, "ms_densify_plan");
   if (rc) return rc;
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
-  if (tmp == nullptr) return ms_exclusive_scan_i32(nullptr, 2 * n, nullptr, nullptr, nullptr, tmp_bytes, stream);
+  MS_CHECK_TMP(tmp, tmp_bytes, scan_tmp_size(2 * n));       // the whole block is the scan's
   MS_CHECK_ARG(scan && counts, "null pointer");
   MS_CHECK_ARG(n == 0 || (prune && split), "null mask");
   hipStream_t s = (hipStream_t)stream;

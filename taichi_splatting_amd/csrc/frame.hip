@@ -112,16 +112,16 @@ static int check_grads(const ms_frame_grads* g, const char* who) {
   return 0;
 }
 
-struct Carve {
-  size_t off = 0;
-  size_t take(size_t bytes) { const size_t o = off; off += align_up(bytes > 0 ? bytes : 1, 256); return o; }
+// the frame's blocks and the direct mapper's scratch give every region a place of its own, empty ones included
+struct FrameCarve : Carve {
+  size_t take(size_t bytes) { return Carve::take(bytes > 0 ? bytes : 1); }
 };
 
 static void frame_layout(const ms_frame_desc* d, ms_frame_layout* L) {
   const FrameGeom g = frame_geom(d);
   const size_t n = (size_t)d->n, k = (size_t)d->k_capacity;
   const bool own_points = !d->projected_input;
-  Carve keep_n, scratch_n, keep_k, scratch_k;
+  FrameCarve keep_n, scratch_n, keep_k, scratch_k;
   L->points7 = keep_n.take(own_points ? n * 7 * g.es : 0);
   L->depth = keep_n.take(own_points ? n * g.es : 0);
   L->colours = keep_n.take(d->sh_degree >= 0 ? n * d->f * g.es : 0);
@@ -470,7 +470,6 @@ extern "C" int ms_map_tiles_direct(const float* points7, const void* depth, int 
   MS_CHECK_ARG(depth_dtype == MS_F32 || depth_dtype == MS_F64, "depth_dtype must be MS_F32 or MS_F64");
   MS_CHECK_ARG(tile_size > 0 && image_w > 0 && image_h > 0, "bad image/tile size");
   MS_CHECK_ARG(image_w % tile_size == 0 && image_h % tile_size == 0, "image size must be padded to the tile size");
-  MS_CHECK_ARG(scratch_bytes != nullptr, "scratch_bytes is null");
   DirectMapGrid g;
   g.w_pad = image_w; g.h_pad = image_h; g.tile_size = tile_size;
   g.tiles_wide = image_w / tile_size;
@@ -484,12 +483,11 @@ extern "C" int ms_map_tiles_direct(const float* points7, const void* depth, int 
   g.alpha_threshold = alpha_threshold;
   MS_CHECK_ARG(!depth16 || g.num_tiles <= 65536, "use_depth16 keys hold a 16 bit tile id: too many tiles");
 
-  Carve c;
+  FrameCarve c;
   const size_t k = (size_t)k_capacity;
   const size_t payload_out = c.take(k * 8), payload_alt = c.take(k * 8), ids_out = c.take(k * 4), ids_alt = c.take(k * 4);
   const size_t hist = c.take(sort_hist_size(k_capacity));
-  if (scratch == nullptr) { *scratch_bytes = c.off; return 0; }
-  if (*scratch_bytes < c.off) { set_error("ms_map_tiles_direct: scratch too small (%zu < %zu)", *scratch_bytes, c.off); return MS_ERR_TMP_TOO_SMALL; }
+  MS_CHECK_TMP(scratch, scratch_bytes, c.off);
   MS_CHECK_ARG(out_tile_ranges && out_counters, "null pointer");
   MS_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "scratch must be 16-byte aligned");
 
@@ -504,8 +502,8 @@ extern "C" int ms_map_tiles_direct(const float* points7, const void* depth, int 
                                                                                       nullptr, out_tile_ranges, words);
   if (v > 0 && k_capacity > 0) {
     MS_CHECK_ARG(points7 && depth && out_overlap_to_point, "null pointer");
-    char* sc = (char*)scratch;
-    const DirectMapBufs bufs{sc + ids_out, sc + ids_alt, (uint64_t*)(sc + payload_out), (uint64_t*)(sc + payload_alt), sc + hist};
+    const DirectMapBufs bufs{at<char>(scratch, ids_out), at<char>(scratch, ids_alt), at<uint64_t>(scratch, payload_out),
+                             at<uint64_t>(scratch, payload_alt), at<char>(scratch, hist)};
     MS_TRY(direct_map_enqueue(points7, depth, depth_dtype, cum, v, g, depth16, ndc_near > 0.0 ? ndc_near : 0.0, ndc_far,
                               k_capacity, out_counters, bufs, out_tile_ranges, out_overlap_to_point, nullptr, s));
   }

@@ -421,13 +421,7 @@ extern "C" int ms_normal_consistency_fwd(const void* accum, const void* pixel_we
                                          void* depth_normals, void* stream) {
   const int rc = nc_check(H, W, F, depth_offset, alpha_offset, normal_offset, dtype, alpha_min, "ms_normal_consistency_fwd");
   if (rc) return rc;
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
-  const size_t need = align_up((size_t)(div_up(W, NC_TW) * div_up(H, NC_TH)) * sizeof(double), 256);
-  if (tmp == nullptr) { *tmp_bytes = need; return 0; }
-  if (*tmp_bytes < need) {
-    set_error("ms_normal_consistency_fwd: tmp_bytes %zu < %zu", *tmp_bytes, need);
-    return MS_ERR_TMP_TOO_SMALL;
-  }
+  MS_CHECK_TMP(tmp, tmp_bytes, Carve::one((size_t)(div_up(W, NC_TW) * div_up(H, NC_TH)) * sizeof(double)));
   MS_CHECK_ARG(accum && projection && out_loss, "null pointer");
   const NcDims dm{H, W, F, depth_offset, alpha_offset, normal_offset};
   hipStream_t s = (hipStream_t)stream;

@@ -207,10 +207,11 @@ struct KMeansAssignScratch {
 
 static KMeansAssignScratch kmeans_assign_scratch(int d, int k) {
   const size_t kp = (size_t)kmeans_padded_k(k);
+  Carve c;
   KMeansAssignScratch s;
-  s.packed = 0;
-  s.norms = align_up(kp * (size_t)kmeans_padded_d(d) * sizeof(float), 256);
-  s.total = s.norms + align_up(kp * sizeof(float), 256);
+  s.packed = c.take(kp * (size_t)kmeans_padded_d(d) * sizeof(float));
+  s.norms = c.take(kp * sizeof(float));
+  s.total = c.off;
   return s;
 }
 
@@ -326,23 +327,22 @@ struct KMeansUpdateScratch {
   size_t keys_in, vals_in, keys_out, vals_out, start, chunk_off, partial, sort, sort_bytes, total;
 };
 
-static int kmeans_update_scratch(int64_t n, int d, int k, KMeansUpdateScratch* s) {
-  const size_t pairs = align_up((size_t)n * 4, 256), offs = align_up(((size_t)k + 1) * 4, 256);
+static KMeansUpdateScratch kmeans_update_scratch(int64_t n, int d, int k) {
+  const size_t pairs = (size_t)n * 4, offs = ((size_t)k + 1) * 4;
   const size_t max_chunks = (size_t)div_up(n, KM_UPDATE_CHUNK) + (size_t)k;
-  size_t sort_bytes = 0;
-  const int rc = ms_radix_sort_pairs(nullptr, nullptr, nullptr, nullptr, n, 4, 0, 16, nullptr, &sort_bytes, nullptr);
-  if (rc != 0) return rc;
-  s->keys_in = 0;
-  s->vals_in = s->keys_in + pairs;
-  s->keys_out = s->vals_in + pairs;
-  s->vals_out = s->keys_out + pairs;
-  s->start = s->vals_out + pairs;
-  s->chunk_off = s->start + offs;
-  s->partial = s->chunk_off + offs;
-  s->sort = s->partial + align_up(max_chunks * (size_t)(d + 1) * sizeof(double), 256);
-  s->sort_bytes = sort_bytes;
-  s->total = s->sort + align_up(sort_bytes, 256);
-  return 0;
+  Carve c;
+  KMeansUpdateScratch s;
+  s.keys_in = c.take(pairs);
+  s.vals_in = c.take(pairs);
+  s.keys_out = c.take(pairs);
+  s.vals_out = c.take(pairs);
+  s.start = c.take(offs);
+  s.chunk_off = c.take(offs);
+  s.partial = c.take(max_chunks * (size_t)(d + 1) * sizeof(double));
+  s.sort_bytes = sort_tmp_size(n, 4);
+  s.sort = c.take(s.sort_bytes);
+  s.total = c.off;
+  return s;
 }
 
 }  // namespace ms
@@ -353,22 +353,20 @@ using namespace ms;
   MS_CHECK_ARG(n >= 0, "n < 0");                                                          \
   MS_CHECK_ARG(n < ((int64_t)1 << 31) - KM_UPDATE_CHUNK, "n >= 2^31 - 1024 (indices are int32)"); \
   MS_CHECK_ARG(d >= 1 && d <= KM_MAX_D, "d must be in 1..64");                            \
-  MS_CHECK_ARG(k >= 1 && k <= KM_MAX_K, "k must be in 1..65536");                         \
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null")
+  MS_CHECK_ARG(k >= 1 && k <= KM_MAX_K, "k must be in 1..65536")
 
 extern "C" int ms_kmeans_assign(const float* x, int64_t n, int d, const float* codebook, int k, int32_t* out_index,
                                 float* out_dist2, void* tmp, size_t* tmp_bytes, void* stream) {
   KMEANS_CHECK_SHAPE();
   const KMeansAssignScratch s = kmeans_assign_scratch(d, k);
-  if (tmp == nullptr) { *tmp_bytes = s.total; return 0; }
-  if (*tmp_bytes < s.total) { set_error("ms_kmeans_assign: *tmp_bytes too small (%zu < %zu)", *tmp_bytes, s.total); return MS_ERR_TMP_TOO_SMALL; }
+  MS_CHECK_TMP(tmp, tmp_bytes, s.total);
   if (n == 0) return 0;
   MS_CHECK_ARG(x != nullptr, "x is null");
   MS_CHECK_ARG(codebook != nullptr, "codebook is null");
   MS_CHECK_ARG(out_index != nullptr, "out_index is null");
 
-  float4* packed = (float4*)((char*)tmp + s.packed);
-  float* norms = (float*)((char*)tmp + s.norms);
+  float4* packed = at<float4>(tmp, s.packed);
+  float* norms = at<float>(tmp, s.norms);
   hipStream_t st = (hipStream_t)stream;
   const int dp = kmeans_padded_d(d);
   const int64_t kp = kmeans_padded_k(k);
@@ -392,11 +390,8 @@ extern "C" int ms_kmeans_update(const float* x, const int32_t* index, const floa
                                 float* codebook, int32_t* out_counts, double* out_weight_sums, void* tmp,
                                 size_t* tmp_bytes, void* stream) {
   KMEANS_CHECK_SHAPE();
-  KMeansUpdateScratch s;
-  const int rc = kmeans_update_scratch(n, d, k, &s);
-  if (rc != 0) return rc;
-  if (tmp == nullptr) { *tmp_bytes = s.total; return 0; }
-  if (*tmp_bytes < s.total) { set_error("ms_kmeans_update: *tmp_bytes too small (%zu < %zu)", *tmp_bytes, s.total); return MS_ERR_TMP_TOO_SMALL; }
+  const KMeansUpdateScratch s = kmeans_update_scratch(n, d, k);
+  MS_CHECK_TMP(tmp, tmp_bytes, s.total);
   MS_CHECK_ARG(codebook != nullptr, "codebook is null");
   MS_CHECK_ARG(out_counts != nullptr, "out_counts is null");
   hipStream_t st = (hipStream_t)stream;
@@ -408,20 +403,20 @@ extern "C" int ms_kmeans_update(const float* x, const int32_t* index, const floa
   MS_CHECK_ARG(x != nullptr, "x is null");
   MS_CHECK_ARG(index != nullptr, "index is null");
 
-  char* base = (char*)tmp;
-  uint32_t* keys_in = (uint32_t*)(base + s.keys_in);
-  int32_t* vals_in = (int32_t*)(base + s.vals_in);
-  uint32_t* keys_out = (uint32_t*)(base + s.keys_out);
-  int32_t* vals_out = (int32_t*)(base + s.vals_out);
-  int32_t* start = (int32_t*)(base + s.start);
-  int32_t* chunk_off = (int32_t*)(base + s.chunk_off);
-  double* partial = (double*)(base + s.partial);
+  uint32_t* keys_in = at<uint32_t>(tmp, s.keys_in);
+  int32_t* vals_in = at<int32_t>(tmp, s.vals_in);
+  uint32_t* keys_out = at<uint32_t>(tmp, s.keys_out);
+  int32_t* vals_out = at<int32_t>(tmp, s.vals_out);
+  int32_t* start = at<int32_t>(tmp, s.start);
+  int32_t* chunk_off = at<int32_t>(tmp, s.chunk_off);
+  double* partial = at<double>(tmp, s.partial);
   const unsigned point_blocks = (unsigned)div_up(n, KM_THREADS);
 
   kmeans_pairs_kernel<<<point_blocks, KM_THREADS, 0, st>>>(index, (int)n, k, keys_in, vals_in);
   MS_CHECK_LAUNCH();
   size_t sort_bytes = s.sort_bytes;
-  const int sort_rc = ms_radix_sort_pairs(keys_in, vals_in, keys_out, vals_out, n, 4, 0, 16, base + s.sort, &sort_bytes, stream);
+  const int sort_rc = ms_radix_sort_pairs(keys_in, vals_in, keys_out, vals_out, n, 4, 0, 16,
+                                          at<char>(tmp, s.sort), &sort_bytes, stream);
   if (sort_rc != 0) return sort_rc;
   kmeans_ranges_kernel<<<point_blocks, KM_THREADS, 0, st>>>(keys_out, (int)n, k, start);
   MS_CHECK_LAUNCH();

@@ -53,11 +53,12 @@ struct KnnScratch {
 
 static KnnScratch knn_scratch(int64_t n) {
   const size_t blocks = (size_t)div_up(n, KNN_BLOCK);
+  Carve c;
   KnnScratch s;
-  s.rows = 0;
-  s.lo = align_up((size_t)n * sizeof(float4), 256);
-  s.hi = s.lo + align_up(blocks * sizeof(float4), 256);
-  s.total = s.hi + align_up(blocks * sizeof(float4), 256);
+  s.rows = c.take((size_t)n * sizeof(float4));
+  s.lo = c.take(blocks * sizeof(float4));
+  s.hi = c.take(blocks * sizeof(float4));
+  s.total = c.off;
   return s;
 }
 
@@ -246,18 +247,16 @@ extern "C" int ms_knn_points(const float* points3, const int32_t* order, int64_t
   MS_CHECK_ARG(n >= 0, "n < 0");
   MS_CHECK_ARG(n < ((int64_t)1 << 31), "n >= 2^31 (indices are int32)");
   MS_CHECK_ARG(k >= 1 && k <= 8, "k must be in 1..8");
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
   const KnnScratch s = knn_scratch(n);
-  if (tmp == nullptr) { *tmp_bytes = s.total; return 0; }
-  if (*tmp_bytes < s.total) { set_error("ms_knn_points: *tmp_bytes too small (%zu < %zu)", *tmp_bytes, s.total); return MS_ERR_BAD_ARG; }
+  MS_CHECK_TMP_AS(tmp, tmp_bytes, s.total, MS_ERR_BAD_ARG);   // this entry point's documented code for a short block
   if (n == 0) return 0;
   MS_CHECK_ARG(points3 != nullptr, "points3 is null");
   MS_CHECK_ARG(order != nullptr, "order is null");
   MS_CHECK_ARG(out_dist2 != nullptr, "out_dist2 is null");
 
-  float4* rows = (float4*)((char*)tmp + s.rows);
-  float4* lo = (float4*)((char*)tmp + s.lo);
-  float4* hi = (float4*)((char*)tmp + s.hi);
+  float4* rows = at<float4>(tmp, s.rows);
+  float4* lo = at<float4>(tmp, s.lo);
+  float4* hi = at<float4>(tmp, s.hi);
   const int blocks = (int)div_up(n, KNN_BLOCK);
   hipStream_t st = (hipStream_t)stream;
   knn_gather_blocks_kernel<<<(unsigned)blocks, KNN_BLOCK, 0, st>>>(points3, order, (int)n, rows, lo, hi);

@@ -316,14 +316,8 @@ extern "C" int ms_photometric_fwd(const void* image, const void* target, int H, 
   const int rc = ph_check(H, W, C, dtype, padding, "ms_photometric_fwd", &margin);
   if (rc) return rc;
   MS_CHECK_ARG(lambda >= 0.0 && lambda <= 1.0, "0 <= lambda <= 1 expected");
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
   const dim3 grid = dtype == MS_F32 ? ph_grid<float>(H, W, C) : ph_grid<double>(H, W, C);
-  const size_t need = align_up((size_t)grid.x * grid.y * 2 * sizeof(double), 256);
-  if (tmp == nullptr) { *tmp_bytes = need; return 0; }
-  if (*tmp_bytes < need) {
-    set_error("ms_photometric_fwd: tmp_bytes %zu < %zu", *tmp_bytes, need);
-    return MS_ERR_TMP_TOO_SMALL;
-  }
+  MS_CHECK_TMP(tmp, tmp_bytes, Carve::one((size_t)grid.x * grid.y * 2 * sizeof(double)));
   MS_CHECK_ARG(image && target && out_loss, "null pointer");
   MS_CHECK_ARG((map_a && map_b && map_c) || (!map_a && !map_b && !map_c), "the partial maps come as three or none");
   hipStream_t s = (hipStream_t)stream;

@@ -328,75 +328,53 @@ static int mesh_key_bits(int64_t largest) {
   return bits;
 }
 
+// Scratch layouts.  Empty arrays keep one element (the kernels are handed real addresses at every size).
+static size_t mesh_some(int64_t n) { return (size_t)(n > 0 ? n : 1); }
+
 struct MeshComponentsTmp { size_t status, parent, rank, scan, scan_bytes, total; };
 static MeshComponentsTmp mesh_components_tmp(int64_t v) {
+  Carve c;
   MeshComponentsTmp t;
-  t.status = 0;
-  t.parent = 256;
-  t.rank = t.parent + align_up((size_t)(v > 0 ? v : 1) * 4, 256);
-  t.scan = t.rank + align_up((size_t)(v + 1) * 4, 256);
-  size_t need = 0;
-  ms_exclusive_scan_i32(nullptr, v, nullptr, nullptr, nullptr, &need, nullptr);
-  t.scan_bytes = need;
-  t.total = t.scan + align_up(need, 256);
+  t.status = c.take(4);
+  t.parent = c.take(mesh_some(v) * 4);
+  t.rank = c.take((size_t)(v + 1) * 4);
+  t.scan_bytes = scan_tmp_size(v);
+  t.scan = c.take(t.scan_bytes);
+  t.total = c.off;
   return t;
 }
 
 struct MeshSelectTmp { size_t status, scan, scan_bytes, total; };
 static MeshSelectTmp mesh_select_tmp(int64_t v, int64_t f) {
+  Carve c;
   MeshSelectTmp t;
-  t.status = 0;
-  t.scan = 256;
-  size_t need = 0;
-  ms_exclusive_scan_i32(nullptr, v > f ? v : f, nullptr, nullptr, nullptr, &need, nullptr);
-  t.scan_bytes = need;
-  t.total = t.scan + align_up(need, 256);
+  t.status = c.take(4);
+  t.scan_bytes = scan_tmp_size(v > f ? v : f);
+  t.scan = c.take(t.scan_bytes);
+  t.total = c.off;
   return t;
 }
 
-struct MeshFilterTmp { size_t keys, values, keys_sorted, values_sorted, keep, sort, sort_bytes, total; };
-static MeshFilterTmp mesh_filter_tmp(int64_t k) {
-  MeshFilterTmp t;
-  const size_t column = align_up((size_t)(k > 0 ? k : 1) * 4, 256);
-  t.keys = 0;
-  t.values = column;
-  t.keys_sorted = 2 * column;
-  t.values_sorted = 3 * column;
-  t.keep = 4 * column;
-  t.sort = 5 * column;
-  size_t need = 0;
-  ms_radix_sort_pairs(nullptr, nullptr, nullptr, nullptr, k, 4, 0, 32, nullptr, &need, nullptr);
-  t.sort_bytes = need;
-  t.total = t.sort + align_up(need, 256);
+// keys, values and their sorted copies: `count` 4-byte entries each, then `extra` bytes, then the sort's own scratch
+struct MeshSortTmp { size_t keys, values, keys_sorted, values_sorted, extra, sort, sort_bytes, total; };
+static MeshSortTmp mesh_sort_tmp(int64_t count, size_t extra) {
+  const size_t column = mesh_some(count) * 4;
+  Carve c;
+  MeshSortTmp t;
+  t.keys = c.take(column);
+  t.values = c.take(column);
+  t.keys_sorted = c.take(column);
+  t.values_sorted = c.take(column);
+  t.extra = c.take(extra);
+  t.sort_bytes = sort_tmp_size(count, 4);
+  t.sort = c.take(t.sort_bytes);
+  t.total = c.off;
   return t;
 }
-
-struct MeshNormalsTmp { size_t keys, values, keys_sorted, values_sorted, ranges, sort, sort_bytes, total; };
-static MeshNormalsTmp mesh_normals_tmp(int64_t v, int64_t f) {
-  MeshNormalsTmp t;
-  const int64_t corners = 3 * f;
-  const size_t column = align_up((size_t)(corners > 0 ? corners : 1) * 4, 256);
-  t.keys = 0;
-  t.values = column;
-  t.keys_sorted = 2 * column;
-  t.values_sorted = 3 * column;
-  t.ranges = 4 * column;
-  t.sort = t.ranges + align_up((size_t)(v > 0 ? v : 1) * 8, 256);
-  size_t need = 0;
-  ms_radix_sort_pairs(nullptr, nullptr, nullptr, nullptr, corners, 4, 0, 32, nullptr, &need, nullptr);
-  t.sort_bytes = need;
-  t.total = t.sort + align_up(need, 256);
-  return t;
-}
-
-#define MS_MESH_TMP(layout)                                                                                       \
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");                                                        \
-  if (tmp == nullptr) { *tmp_bytes = (layout).total; return 0; }                                                  \
-  if (*tmp_bytes < (layout).total) {                                                                              \
-    set_error("%s: tmp too small (%zu < %zu)", __func__, *tmp_bytes, (layout).total);                             \
-    return MS_ERR_TMP_TOO_SMALL;                                                                                  \
-  }                                                                                                               \
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes")
+// ms_mesh_component_filter: extra = the keep flags of the k components
+static MeshSortTmp mesh_filter_tmp(int64_t k) { return mesh_sort_tmp(k, mesh_some(k) * 4); }
+// ms_mesh_vertex_normals: sorts the 3 f corners, extra = the (first, last + 1) corner ranges of the v vertices
+static MeshSortTmp mesh_normals_tmp(int64_t v, int64_t f) { return mesh_sort_tmp(3 * f, mesh_some(v) * 8); }
 
 }  // namespace ms
 
@@ -406,16 +384,16 @@ extern "C" int ms_mesh_components(const int32_t* faces, int64_t num_vertices, in
                                   int32_t* face_label, int32_t* head, void* tmp, size_t* tmp_bytes, void* stream) {
   MS_CHECK_ARG(mesh_sizes_ok(num_vertices, num_faces), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected");
   const MeshComponentsTmp lay = mesh_components_tmp(num_vertices);
-  MS_MESH_TMP(lay);
+  MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
+  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
   MS_CHECK_ARG(head != nullptr, "head is null");
   MS_CHECK_ARG((faces && face_label) || num_faces == 0, "null faces or face_label");
   MS_CHECK_ARG(vertex_label || num_vertices == 0, "null vertex_label");
   MS_CHECK_ARG(mesh_aligned4({faces, vertex_label, face_label, head}), "every pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)tmp;
-  int32_t* status = (int32_t*)(base + lay.status);
-  int32_t* parent = (int32_t*)(base + lay.parent);
-  int32_t* rank = (int32_t*)(base + lay.rank);
+  int32_t* status = at<int32_t>(tmp, lay.status);
+  int32_t* parent = at<int32_t>(tmp, lay.parent);
+  int32_t* rank = at<int32_t>(tmp, lay.rank);
   const int32_t v = (int32_t)num_vertices;
   MS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
   MS_CHECK_HIP(hipMemsetAsync(head, 0xff, 2 * sizeof(int32_t), s));        // poisoned: (-1, -1) unless the label kernel ran
@@ -424,7 +402,7 @@ extern "C" int ms_mesh_components(const int32_t* faces, int64_t num_vertices, in
   if (num_vertices > 0) mesh_flatten_kernel<<<mesh_grid(num_vertices), dim3(256), 0, s>>>(parent, vertex_label, v, rank);
   MS_CHECK_LAUNCH();
   size_t scan_bytes = lay.scan_bytes;
-  const int rc = ms_exclusive_scan_i32(rank, num_vertices, rank, nullptr, base + lay.scan, &scan_bytes, stream);
+  const int rc = ms_exclusive_scan_i32(rank, num_vertices, rank, nullptr, at<char>(tmp, lay.scan), &scan_bytes, stream);
   if (rc != 0) return rc;
   mesh_label_kernel<<<mesh_grid(num_vertices > num_faces ? num_vertices : num_faces), dim3(256), 0, s>>>(
       faces, v, num_faces, parent, rank, vertex_label, face_label, status, head);
@@ -458,18 +436,18 @@ extern "C" int ms_mesh_component_filter(const int32_t* face_count, int64_t num_c
   MS_CHECK_ARG(num_faces >= 0 && num_faces <= MS_MESH_MAX_CORNERS / 3, "0 <= 3 T <= 2^31 - 1 expected");
   MS_CHECK_ARG(min_faces >= 1, "min_faces >= 1 expected");
   MS_CHECK_ARG(keep_largest >= 0, "keep_largest >= 1 (or 0: every component) expected");
-  const MeshFilterTmp lay = mesh_filter_tmp(num_components);
-  MS_MESH_TMP(lay);
+  const MeshSortTmp lay = mesh_filter_tmp(num_components);
+  MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
+  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
   if (num_faces == 0) return 0;
   MS_CHECK_ARG(face_label && face_mask && (face_count || num_components == 0), "null pointer");
   MS_CHECK_ARG(mesh_aligned4({face_count, face_label}), "face_count and face_label must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)tmp;
-  uint32_t* keys = (uint32_t*)(base + lay.keys);
-  int32_t* values = (int32_t*)(base + lay.values);
-  uint32_t* keys_sorted = (uint32_t*)(base + lay.keys_sorted);
-  int32_t* values_sorted = (int32_t*)(base + lay.values_sorted);
-  int32_t* keep = (int32_t*)(base + lay.keep);
+  uint32_t* keys = at<uint32_t>(tmp, lay.keys);
+  int32_t* values = at<int32_t>(tmp, lay.values);
+  uint32_t* keys_sorted = at<uint32_t>(tmp, lay.keys_sorted);
+  int32_t* values_sorted = at<int32_t>(tmp, lay.values_sorted);
+  int32_t* keep = at<int32_t>(tmp, lay.extra);
   const int32_t k = (int32_t)num_components;
   if (num_components > 0) {
     mesh_filter_keys_kernel<<<mesh_grid(num_components), dim3(256), 0, s>>>(face_count, k, min_faces, keep_largest == 0, keys,
@@ -477,8 +455,8 @@ extern "C" int ms_mesh_component_filter(const int32_t* face_count, int64_t num_c
     MS_CHECK_LAUNCH();
     if (keep_largest > 0) {
       size_t sort_bytes = lay.sort_bytes;
-      const int rc = ms_radix_sort_pairs(keys, values, keys_sorted, values_sorted, num_components, 4, 0, 32, base + lay.sort,
-                                         &sort_bytes, stream);
+      const int rc = ms_radix_sort_pairs(keys, values, keys_sorted, values_sorted, num_components, 4, 0, 32,
+                                         at<char>(tmp, lay.sort), &sort_bytes, stream);
       if (rc != 0) return rc;
       const int64_t take = keep_largest < num_components ? keep_largest : num_components;
       mesh_filter_take_kernel<<<mesh_grid(take), dim3(256), 0, s>>>(keys_sorted, values_sorted, take, k, keep);
@@ -494,13 +472,13 @@ extern "C" int ms_mesh_select_plan(const int32_t* faces, const uint8_t* face_mas
                                    void* stream) {
   MS_CHECK_ARG(mesh_sizes_ok(num_vertices, num_faces), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected");
   const MeshSelectTmp lay = mesh_select_tmp(num_vertices, num_faces);
-  MS_MESH_TMP(lay);
+  MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
+  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
   MS_CHECK_ARG(vertex_scan && face_scan && head, "null vertex_scan, face_scan or head");
   MS_CHECK_ARG((faces && face_mask) || num_faces == 0, "null faces or face_mask");
   MS_CHECK_ARG(mesh_aligned4({faces, vertex_scan, face_scan, head}), "every int32 pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)tmp;
-  int32_t* status = (int32_t*)(base + lay.status);
+  int32_t* status = at<int32_t>(tmp, lay.status);
   MS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
   MS_CHECK_HIP(hipMemsetAsync(head, 0xff, 3 * sizeof(int32_t), s));        // poisoned until mesh_head_kernel ran
   MS_CHECK_HIP(hipMemsetAsync(vertex_scan, 0, (size_t)(num_vertices + 1) * 4, s));
@@ -511,9 +489,10 @@ extern "C" int ms_mesh_select_plan(const int32_t* faces, const uint8_t* face_mas
     MS_CHECK_LAUNCH();
   }
   size_t scan_bytes = lay.scan_bytes;
-  int rc = ms_exclusive_scan_i32(vertex_scan, num_vertices, vertex_scan, nullptr, base + lay.scan, &scan_bytes, stream);
+  char* scan_tmp = at<char>(tmp, lay.scan);
+  int rc = ms_exclusive_scan_i32(vertex_scan, num_vertices, vertex_scan, nullptr, scan_tmp, &scan_bytes, stream);
   if (rc != 0) return rc;
-  rc = ms_exclusive_scan_i32(face_scan, num_faces, face_scan, nullptr, base + lay.scan, &scan_bytes, stream);
+  rc = ms_exclusive_scan_i32(face_scan, num_faces, face_scan, nullptr, scan_tmp, &scan_bytes, stream);
   if (rc != 0) return rc;
   mesh_head_kernel<<<dim3(1), dim3(64), 0, s>>>(vertex_scan + num_vertices, face_scan + num_faces, status, head);
   MS_CHECK_LAUNCH();
@@ -543,26 +522,26 @@ extern "C" int ms_mesh_select_gather(const float* vertices, const float* colours
 extern "C" int ms_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t num_vertices, int64_t num_faces,
                                       float* out_sums, float* out_normals, void* tmp, size_t* tmp_bytes, void* stream) {
   MS_CHECK_ARG(mesh_sizes_ok(num_vertices, num_faces), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected");
-  const MeshNormalsTmp lay = mesh_normals_tmp(num_vertices, num_faces);
-  MS_MESH_TMP(lay);
+  const MeshSortTmp lay = mesh_normals_tmp(num_vertices, num_faces);
+  MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
+  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
   if (num_vertices == 0) return 0;
   MS_CHECK_ARG(vertices && (faces || num_faces == 0), "null vertices or faces");
   MS_CHECK_ARG(out_sums || out_normals, "out_sums and out_normals are both null");
   MS_CHECK_ARG(mesh_aligned4({vertices, faces, out_sums, out_normals}), "every pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)tmp;
-  uint32_t* keys = (uint32_t*)(base + lay.keys);
-  int32_t* values = (int32_t*)(base + lay.values);
-  uint32_t* keys_sorted = (uint32_t*)(base + lay.keys_sorted);
-  int32_t* values_sorted = (int32_t*)(base + lay.values_sorted);
-  int32_t* ranges = (int32_t*)(base + lay.ranges);
+  uint32_t* keys = at<uint32_t>(tmp, lay.keys);
+  int32_t* values = at<int32_t>(tmp, lay.values);
+  uint32_t* keys_sorted = at<uint32_t>(tmp, lay.keys_sorted);
+  int32_t* values_sorted = at<int32_t>(tmp, lay.values_sorted);
+  int32_t* ranges = at<int32_t>(tmp, lay.extra);
   const int64_t corners = 3 * num_faces;
   if (corners > 0) {
     mesh_corner_keys_kernel<<<mesh_grid(corners), dim3(256), 0, s>>>(faces, (int32_t)num_vertices, corners, keys, values);
     MS_CHECK_LAUNCH();
     size_t sort_bytes = lay.sort_bytes;
     const int rc = ms_radix_sort_pairs(keys, values, keys_sorted, values_sorted, corners, 4, 0, mesh_key_bits(num_vertices),
-                                       base + lay.sort, &sort_bytes, stream);
+                                       at<char>(tmp, lay.sort), &sort_bytes, stream);
     if (rc != 0) return rc;
   }
   const int rc = ms_find_ranges(keys_sorted, corners, 4, 0, num_vertices, ranges, stream);

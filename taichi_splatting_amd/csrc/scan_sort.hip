@@ -166,7 +166,7 @@ scan_downsweep_self_kernel(const int32_t* __restrict__ in, int64_t n, const int3
   }
 }
 
-static size_t scan_tmp_bytes(int64_t n) { return align_up((size_t)div_up(n > 0 ? n : 1, SCAN_TILE) * sizeof(int32_t), 256); }
+size_t scan_tmp_size(int64_t n) { return Carve::one((size_t)div_up(n > 0 ? n : 1, SCAN_TILE) * sizeof(int32_t)); }
 
 // out has n + 1 entries (out[n] = total).  in and out may NOT alias unless identical ranges are
 // intended (in == out is allowed: every block reads its tile before writing it).
@@ -512,19 +512,17 @@ struct SortTmp {
 // adaptive (radix_sort_depth_adaptive): a second alternate pair of buffers and the per-block OR / AND words
 static SortTmp sort_tmp_layout(int64_t n, int key_bytes, bool adaptive = false) {
   const int64_t blocks = div_up(n > 0 ? n : 1, RS_TILE);
+  const size_t keys = (size_t)n * key_bytes, vals = (size_t)n * sizeof(int32_t);
+  Carve c;
   SortTmp t;
-  size_t off = 0;
-  t.hist_off = off; off += align_up((size_t)(RS_RADIX * blocks + 1) * sizeof(int32_t), 256);
-  t.scan_off = off; off += align_up((size_t)RS_RADIX * sizeof(int32_t), 256);      // digit totals
-  t.keys_off = off; off += align_up((size_t)n * key_bytes, 256);
-  t.vals_off = off; off += align_up((size_t)n * sizeof(int32_t), 256);
-  t.keys2_off = t.vals2_off = t.vary_off = off;
-  if (adaptive) {
-    t.keys2_off = off; off += align_up((size_t)n * key_bytes, 256);
-    t.vals2_off = off; off += align_up((size_t)n * sizeof(int32_t), 256);
-    t.vary_off = off; off += align_up((size_t)(64 + 2 * blocks) * sizeof(uint32_t), 256);
-  }
-  t.total = off;
+  t.hist_off = c.take((size_t)(RS_RADIX * blocks + 1) * sizeof(int32_t));
+  t.scan_off = c.take((size_t)RS_RADIX * sizeof(int32_t));      // digit totals
+  t.keys_off = c.take(keys);
+  t.vals_off = c.take(vals);
+  t.keys2_off = c.take(adaptive ? keys : 0);
+  t.vals2_off = c.take(adaptive ? vals : 0);
+  t.vary_off = c.take(adaptive ? (size_t)(64 + 2 * blocks) * sizeof(uint32_t) : 0);
+  t.total = c.off;
   return t;
 }
 
@@ -800,7 +798,6 @@ find_ranges_ids_kernel(const IdT* __restrict__ ids, int64_t capacity, const int3
 }
 
 // ---- launchers for the frame executor (frame_internal.h) ----------------------------------------------------------
-size_t scan_tmp_size(int64_t n) { return scan_tmp_bytes(n); }
 size_t sort_tmp_size(int64_t n, int key_bytes, bool adaptive) { return sort_tmp_layout(n, key_bytes, adaptive).total; }
 
 void exclusive_scan_launch(const int32_t* in, int64_t n, int32_t* out, int32_t* total_host, void* tmp, hipStream_t s,
@@ -865,10 +862,7 @@ using namespace ms;
 extern "C" int ms_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* total_host,
                                      void* tmp, size_t* tmp_bytes, void* stream) {
   MS_CHECK_ARG(n >= 0, "n < 0");
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
-  const size_t need = scan_tmp_bytes(n);
-  if (tmp == nullptr) { *tmp_bytes = need; return 0; }
-  if (*tmp_bytes < need) { set_error("ms_exclusive_scan_i32: tmp too small (%zu < %zu)", *tmp_bytes, need); return MS_ERR_TMP_TOO_SMALL; }
+  MS_CHECK_TMP(tmp, tmp_bytes, scan_tmp_size(n));
   MS_CHECK_ARG(out != nullptr, "out is null");
   MS_CHECK_ARG(n == 0 || in != nullptr, "in is null");
   if (n == 0) {
@@ -887,10 +881,7 @@ extern "C" int ms_radix_sort_pairs(const void* keys_in, const int32_t* values_in
   MS_CHECK_ARG(n >= 0, "n < 0");
   MS_CHECK_ARG(key_bytes == 4 || key_bytes == 8, "key_bytes must be 4 or 8");
   MS_CHECK_ARG(begin_bit >= 0 && end_bit >= begin_bit && end_bit <= key_bytes * 8, "bad bit range");
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
-  const size_t need = sort_tmp_layout(n, key_bytes).total;
-  if (tmp == nullptr) { *tmp_bytes = need; return 0; }
-  if (*tmp_bytes < need) { set_error("ms_radix_sort_pairs: tmp too small (%zu < %zu)", *tmp_bytes, need); return MS_ERR_TMP_TOO_SMALL; }
+  MS_CHECK_TMP(tmp, tmp_bytes, sort_tmp_size(n, key_bytes));
   if (n == 0) return 0;
   MS_CHECK_ARG(keys_in && values_in && keys_out && values_out, "null pointer");
   if (key_bytes == 4)
@@ -906,10 +897,7 @@ extern "C" int ms_depth_argsort(const void* depth, int64_t v, int depth16, doubl
                                size_t* tmp_bytes, void* stream) {
   MS_CHECK_ARG(v >= 0, "v < 0");
   MS_CHECK_ARG(dtype == MS_F32 || dtype == MS_F64, "dtype must be MS_F32 or MS_F64");
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
-  const size_t need = sort_tmp_layout(v, 4).total;
-  if (tmp == nullptr) { *tmp_bytes = need; return 0; }
-  if (*tmp_bytes < need) { set_error("ms_depth_argsort: tmp too small (%zu < %zu)", *tmp_bytes, need); return MS_ERR_TMP_TOO_SMALL; }
+  MS_CHECK_TMP(tmp, tmp_bytes, sort_tmp_size(v, 4));
   if (v == 0) return 0;
   MS_CHECK_ARG(depth && out_sorted_keys && out_order, "null pointer");
   const int end_bit = depth16 ? 16 : 32;

@@ -154,10 +154,11 @@ struct ShCodedScratch {
 
 static ShCodedScratch sh_coded_scratch(int64_t n, int64_t num_chunks, int degree) {
   const size_t row = 3 * (size_t)((degree + 1) * (degree + 1) - 1);
+  Carve c;
   ShCodedScratch s;
-  s.partial = 0;
-  s.records = align_up((size_t)(num_chunks > 0 ? num_chunks : 1) * row * sizeof(double), 256);
-  s.total = s.records + align_up((size_t)n * SC_RECORD * sizeof(float), 256);
+  s.partial = c.take((size_t)(num_chunks > 0 ? num_chunks : 1) * row * sizeof(double));
+  s.records = c.take((size_t)n * SC_RECORD * sizeof(float));
+  s.total = c.off;
   return s;
 }
 
@@ -202,10 +203,8 @@ extern "C" int ms_sh_coded_bwd(const float* positions, const float* cam_pos, con
                                size_t* tmp_bytes, void* stream) {
   SH_CODED_CHECK_SHAPE();
   MS_CHECK_ARG(num_chunks >= 0 && num_chunks <= n, "num_chunks must be in 0..n (a chunk holds at least one entry)");
-  MS_CHECK_ARG(tmp_bytes != nullptr, "tmp_bytes is null");
   const ShCodedScratch s = sh_coded_scratch(n, num_chunks, sh_degree);
-  if (tmp == nullptr) { *tmp_bytes = s.total; return 0; }
-  if (*tmp_bytes < s.total) { set_error("ms_sh_coded_bwd: *tmp_bytes too small (%zu < %zu)", *tmp_bytes, s.total); return MS_ERR_TMP_TOO_SMALL; }
+  MS_CHECK_TMP(tmp, tmp_bytes, s.total);
   if (g_dc == nullptr && g_codebook == nullptr) return 0;
 
   hipStream_t st = (hipStream_t)stream;
@@ -224,8 +223,8 @@ extern "C" int ms_sh_coded_bwd(const float* positions, const float* cam_pos, con
     MS_CHECK_ARG(rank != nullptr, "rank is null");
   }
 
-  double* partial = (double*)((char*)tmp + s.partial);
-  float* recs = (float*)((char*)tmp + s.records);
+  double* partial = at<double>(tmp, s.partial);
+  float* recs = at<float>(tmp, s.records);
   const dim3 block(SC_THREADS), point_grid((unsigned)div_up(n, SC_THREADS));
   if (g_codebook != nullptr) {
     sh_coded_prep_kernel<true><<<point_grid, block, 0, st>>>(positions, cam_pos, out, g_out, rank, (int)n, g_dc, recs);

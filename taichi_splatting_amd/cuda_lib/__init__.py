@@ -5,7 +5,6 @@ call sites keep working; ``hip_lib`` is an alias.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -20,10 +19,6 @@ def check_cuda(name, arg):
   assert arg.is_cuda, f"{name}: device must be a cuda device, got {arg.device}"
 
 
-def _scratch(nbytes: int, device) -> torch.Tensor:
-  return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
-
-
 def full_cumsum(x: torch.Tensor, return_total: bool = True) -> Tuple[torch.Tensor, int]:
   """Exclusive scan with the total appended: returns (out (n+1,), total) — full_cumsum.cu:51-67.
 
@@ -33,16 +28,10 @@ def full_cumsum(x: torch.Tensor, return_total: bool = True) -> Tuple[torch.Tenso
   assert x.dtype == torch.int32 and x.ndim == 1, "full_cumsum: int32 vector expected"
   if x.shape[0] == 0:
     return x.new_zeros((1,)), 0
-  lib = _lib.load()
   x = x.contiguous()
   n = x.shape[0]
   out = x.new_empty((n + 1,))
-  nbytes = ctypes.c_size_t(0)
-  stream = _lib.current_stream(x.device)
-  _lib.check(lib.ms_exclusive_scan_i32(None, n, None, None, None, ctypes.byref(nbytes), stream), "full_cumsum")
-  tmp = _scratch(nbytes.value, x.device)
-  _lib.check(lib.ms_exclusive_scan_i32(x.data_ptr(), n, out.data_ptr(), None, tmp.data_ptr(),
-                                       ctypes.byref(nbytes), stream), "full_cumsum")
+  _lib.exclusive_scan(x.data_ptr(), n, out.data_ptr(), x.device, "full_cumsum")
   total = int(out[n].item()) if return_total else -1
   return out, total
 
@@ -86,14 +75,10 @@ def radix_sort_pairs(keys: torch.Tensor, values: torch.Tensor, start_bit: int = 
   if n > 0:
     lib = _lib.load()
     values = values.contiguous()
-    nbytes = ctypes.c_size_t(0)
     stream = _lib.current_stream(work.device)
-    _lib.check(lib.ms_radix_sort_pairs(None, None, None, None, n, key_bytes, start_bit, end_bit,
-                                       None, ctypes.byref(nbytes), stream), "radix_sort_pairs")
-    tmp = _scratch(nbytes.value, work.device)
-    _lib.check(lib.ms_radix_sort_pairs(work.data_ptr(), values.data_ptr(), keys_out.data_ptr(),
-                                       values_out.data_ptr(), n, key_bytes, start_bit, end_bit,
-                                       tmp.data_ptr(), ctypes.byref(nbytes), stream), "radix_sort_pairs")
+    _lib.run_with_scratch(lambda tmp, size: lib.ms_radix_sort_pairs(
+      work.data_ptr(), values.data_ptr(), keys_out.data_ptr(), values_out.data_ptr(), n, key_bytes, start_bit, end_bit,
+      tmp, size, stream), work.device, "radix_sort_pairs")
   if flip:
     keys_out = keys_out ^ sign
   if keys_out.dtype != orig_dtype:

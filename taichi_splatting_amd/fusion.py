@@ -251,15 +251,11 @@ class TSDFVolume:
     word = torch.empty((n,), dtype=torch.int32, device=self.device)
     vscan = torch.empty((n + 1,), dtype=torch.int32, device=self.device)
     tscan = torch.empty((n + 1,), dtype=torch.int32, device=self.device)
-    need = ctypes.c_size_t(0)
-    _lib.check(lib.ms_exclusive_scan_i32(None, n, None, None, None, ctypes.byref(need), stream), "extract_mesh")
-    tmp = torch.empty((max(need.value, 1),), dtype=torch.uint8, device=self.device)
     totals = torch.zeros((2,), dtype=torch.int32).pin_memory()
     _lib.check(lib.ms_tsdf_classify(tsdf.data_ptr(), weight.data_ptr(), nx, ny, nz, min_weight, word.data_ptr(),
                                     vscan.data_ptr(), tscan.data_ptr(), stream), "extract_mesh")
     for slot, scan in enumerate((vscan, tscan)):
-      _lib.check(lib.ms_exclusive_scan_i32(scan.data_ptr(), n, scan.data_ptr(), totals.data_ptr() + 4 * slot, tmp.data_ptr(),
-                                           ctypes.byref(need), stream), "extract_mesh")
+      _lib.exclusive_scan(scan.data_ptr(), n, scan.data_ptr(), self.device, "extract_mesh", totals.data_ptr() + 4 * slot)
     torch.cuda.current_stream(self.device).synchronize()          # the one host read: V and T size the outputs
     num_vertices, num_faces = int(totals[0]), int(totals[1])
     vertices = torch.empty((num_vertices, 3), dtype=torch.float32, device=self.device)

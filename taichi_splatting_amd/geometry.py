@@ -10,7 +10,6 @@ and are bitwise reproducible.
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import Optional
 
@@ -237,15 +236,11 @@ def normal_consistency_forward(accum, offsets, projection, pixel_weight, alpha_m
   lib = _lib.load()
   h, w, f = accum.shape
   dtype, stream = _lib.dtype_code(accum.dtype), _lib.current_stream(accum.device)
-  need = ctypes.c_size_t(0)
-  _lib.check(lib.ms_normal_consistency_fwd(None, None, None, h, w, f, *offsets, dtype, alpha_min, None, ctypes.byref(need),
-                                           None, None, stream), "normal_consistency_loss")
-  tmp = torch.empty((need.value,), dtype=torch.uint8, device=accum.device)
   out = torch.empty((1,), dtype=accum.dtype, device=accum.device)
   depth_normals = torch.empty((h, w, 3), dtype=accum.dtype, device=accum.device) if want_normals else None
-  _lib.check(lib.ms_normal_consistency_fwd(_lib.ptr(accum), _lib.ptr(pixel_weight), _lib.ptr(projection), h, w, f, *offsets,
-                                           dtype, alpha_min, tmp.data_ptr(), ctypes.byref(need), out.data_ptr(),
-                                           _lib.ptr(depth_normals), stream), "normal_consistency_loss")
+  _lib.run_with_scratch(lambda tmp, size: lib.ms_normal_consistency_fwd(
+    _lib.ptr(accum), _lib.ptr(pixel_weight), _lib.ptr(projection), h, w, f, *offsets, dtype, alpha_min, tmp, size,
+    out.data_ptr(), _lib.ptr(depth_normals), stream), accum.device, "normal_consistency_loss")
   return out[0], depth_normals
 
 

@@ -9,7 +9,6 @@ into ``frame.FrameGraph`` / ``torch.cuda.graph`` with the rest of a training ste
 """
 from __future__ import annotations
 
-import ctypes
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -49,18 +48,15 @@ def photometric_forward(x: torch.Tensor, y: torch.Tensor, ssim_weight: float, pa
   h, w, c = x.shape
   dtype, pad = _lib.dtype_code(x.dtype), PADDING[padding]
   stream = _lib.current_stream(x.device)
-  need = ctypes.c_size_t(0)
-  _lib.check(lib.ms_photometric_fwd(None, None, h, w, c, dtype, pad, ssim_weight, None, None, None, None,
-                                    ctypes.byref(need), None, stream), "l1_ssim_loss")
-  tmp = torch.empty((need.value,), dtype=torch.uint8, device=x.device)
   out = torch.empty((3,), dtype=x.dtype, device=x.device)
   maps, pointers = None, (None, None, None)
   if want_maps:
     margin = 0 if padding == 'same' else WINDOW // 2
     maps = torch.empty((3, h - 2 * margin, w - 2 * margin, c), dtype=x.dtype, device=x.device)
     pointers = tuple(maps[k].data_ptr() for k in range(3))
-  _lib.check(lib.ms_photometric_fwd(_lib.ptr(x), _lib.ptr(y), h, w, c, dtype, pad, ssim_weight, *pointers,
-                                    tmp.data_ptr(), ctypes.byref(need), out.data_ptr(), stream), "l1_ssim_loss")
+  _lib.run_with_scratch(lambda tmp, size: lib.ms_photometric_fwd(
+    _lib.ptr(x), _lib.ptr(y), h, w, c, dtype, pad, ssim_weight, *pointers, tmp, size, out.data_ptr(), stream),
+    x.device, "l1_ssim_loss")
   return out, maps
 
 

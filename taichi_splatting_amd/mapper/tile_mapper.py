@@ -18,7 +18,6 @@ generated in point order (tile, depth bits, point index) at a fraction of the so
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from numbers import Integral
 from typing import Optional, Tuple
@@ -93,19 +92,12 @@ def map_to_tiles_strip(gaussians: torch.Tensor, depth: torch.Tensor,
     if v == 0:
       return torch.empty((0,), dtype=torch.int32, device=device), tile_ranges.zero_()
 
-    def scratch(nbytes):
-      return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
-
     def sort_pairs(keys_in, vals_in, key_bytes, begin_bit, end_bit):
       n = keys_in.shape[0]
       keys_out, vals_out = torch.empty_like(keys_in), torch.empty_like(vals_in)
-      nb = ctypes.c_size_t(0)
-      _lib.check(lib.ms_radix_sort_pairs(None, None, None, None, n, key_bytes, begin_bit, end_bit, None,
-                                         ctypes.byref(nb), stream), "map_to_tiles")
-      tmp = scratch(nb.value)
-      _lib.check(lib.ms_radix_sort_pairs(keys_in.data_ptr(), vals_in.data_ptr(), keys_out.data_ptr(),
-                                         vals_out.data_ptr(), n, key_bytes, begin_bit, end_bit, tmp.data_ptr(),
-                                         ctypes.byref(nb), stream), "map_to_tiles")
+      _lib.run_with_scratch(lambda tmp, size: lib.ms_radix_sort_pairs(
+        keys_in.data_ptr(), vals_in.data_ptr(), keys_out.data_ptr(), vals_out.data_ptr(), n, key_bytes, begin_bit, end_bit,
+        tmp, size, stream), device, "map_to_tiles")
       return keys_out, vals_out
 
     near, far = (0.0, 0.0) if ndc_range is None else (float(ndc_range[0]), float(ndc_range[1]))
@@ -113,11 +105,7 @@ def map_to_tiles_strip(gaussians: torch.Tensor, depth: torch.Tensor,
 
     def exclusive_scan(counts, want_total):
       cum = torch.empty((v + 1,), dtype=torch.int32, device=device)
-      nbytes = ctypes.c_size_t(0)
-      _lib.check(lib.ms_exclusive_scan_i32(None, v, None, None, None, ctypes.byref(nbytes), stream), "map_to_tiles")
-      tmp = scratch(nbytes.value)
-      _lib.check(lib.ms_exclusive_scan_i32(counts.data_ptr(), v, cum.data_ptr(), None, tmp.data_ptr(),
-                                           ctypes.byref(nbytes), stream), "map_to_tiles")
+      _lib.exclusive_scan(counts.data_ptr(), v, cum.data_ptr(), device, "map_to_tiles")
       return cum, (int(cum[v].item()) if want_total else None)
 
     def checked(total):
@@ -150,10 +138,7 @@ def map_to_tiles_strip(gaussians: torch.Tensor, depth: torch.Tensor,
       args = (points.data_ptr(), depths.data_ptr(), _lib.dtype_code(depths.dtype), cum.data_ptr(), v, w_pad, h_pad, tile_size,
               config.alpha_threshold, row_begin, row_end, int(use_depth16), near, far, total, overlap_to_point.data_ptr(),
               tile_ranges.data_ptr(), counters.data_ptr())
-      nb = ctypes.c_size_t(0)
-      _lib.check(lib.ms_map_tiles_direct(*args, None, ctypes.byref(nb), stream), "map_to_tiles")
-      tmp = scratch(nb.value)
-      _lib.check(lib.ms_map_tiles_direct(*args, tmp.data_ptr(), ctypes.byref(nb), stream), "map_to_tiles")
+      _lib.run_with_scratch(lambda tmp, size: lib.ms_map_tiles_direct(*args, tmp, size, stream), device, "map_to_tiles")
       return overlap_to_point, tile_ranges
 
     assert method == 'presort', f"map_to_tiles: unknown method {method!r}"
@@ -162,13 +147,9 @@ def map_to_tiles_strip(gaussians: torch.Tensor, depth: torch.Tensor,
     #    the K overlaps; the first pass makes the keys from the depths itself (ms_depth_argsort)
     sorted_keys = torch.empty((v,), dtype=torch.int32, device=device)
     order = torch.empty((v,), dtype=torch.int32, device=device)
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.ms_depth_argsort(None, v, int(use_depth16), near, far, _lib.dtype_code(depths.dtype), None, None, None,
-                                    ctypes.byref(nb), stream), "map_to_tiles")
-    tmp = scratch(nb.value)
-    _lib.check(lib.ms_depth_argsort(depths.data_ptr(), v, int(use_depth16), near, far, _lib.dtype_code(depths.dtype),
-                                    sorted_keys.data_ptr(), order.data_ptr(), tmp.data_ptr(), ctypes.byref(nb), stream),
-               "map_to_tiles")
+    _lib.run_with_scratch(lambda tmp, size: lib.ms_depth_argsort(
+      depths.data_ptr(), v, int(use_depth16), near, far, _lib.dtype_code(depths.dtype), sorted_keys.data_ptr(),
+      order.data_ptr(), tmp, size, stream), device, "map_to_tiles")
 
     # 3. overlap counts again, in depth order, with the depth-ordered copy of the rows the emit re-reads linearly
     ordered = torch.empty((v, 7), dtype=torch.float32, device=device)

@@ -14,7 +14,6 @@ per-component areas, float64 meshes, gradients and more than one GPU.
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass, replace
 import operator
 from typing import Optional, Tuple, Union
@@ -66,13 +65,6 @@ def _check_mesh(mesh, what: str) -> Tuple[torch.Tensor, torch.Tensor, int, int]:
   return vertices.detach(), faces.detach(), num_vertices, num_faces
 
 
-def _tmp(query, device) -> Tuple[torch.Tensor, ctypes.c_size_t]:
-  """the scratch block of a call: ``query(tmp_pointer, byref(size))`` with a NULL pointer reports the size"""
-  need = ctypes.c_size_t(0)
-  _lib.check(query(None, ctypes.byref(need)), "mesh scratch size")
-  return torch.empty((max(need.value, 1),), dtype=torch.uint8, device=device), need      # torch allocations are 512-byte aligned
-
-
 def _status(status: int, what: str, num_vertices: int):
   if status < 0:
     raise RuntimeError(f"{what}: the device never reported back (the status word still holds its poison value {status})")
@@ -111,8 +103,7 @@ def mesh_components(mesh: TriangleMesh) -> MeshComponents:
   head = torch.empty((2,), dtype=torch.int32, device=device)
   call = lambda tmp, size: lib.ms_mesh_components(faces.data_ptr(), num_vertices, num_faces, vertex_label.data_ptr(),
                                                   face_label.data_ptr(), head.data_ptr(), tmp, size, stream)
-  tmp, size = _tmp(call, device)
-  _lib.check(call(tmp.data_ptr(), ctypes.byref(size)), "mesh_components")
+  _lib.run_with_scratch(call, device, "mesh_components")
   count, status = (int(x) for x in head.cpu())                       # the one host read: K and the status word
   _status(status, "mesh_components", num_vertices)
   vertex_count = torch.empty((count,), dtype=torch.int32, device=device)
@@ -146,8 +137,7 @@ def select_faces(mesh: TriangleMesh, face_mask: torch.Tensor) -> TriangleMesh:
   head = torch.empty((3,), dtype=torch.int32, device=device)
   call = lambda tmp, size: lib.ms_mesh_select_plan(faces.data_ptr(), mask.data_ptr(), num_vertices, num_faces,
                                                    vertex_scan.data_ptr(), face_scan.data_ptr(), head.data_ptr(), tmp, size, stream)
-  tmp, size = _tmp(call, device)
-  _lib.check(call(tmp.data_ptr(), ctypes.byref(size)), "select_faces")
+  _lib.run_with_scratch(call, device, "select_faces")
   new_vertices, new_faces, status = (int(x) for x in head.cpu())      # the one host read
   _status(status, "select_faces", num_vertices)
   out_vertices = torch.empty((new_vertices, 3), dtype=torch.float32, device=device)
@@ -180,8 +170,7 @@ def remove_small_components(mesh: TriangleMesh, min_faces: int = 1, keep_largest
   call = lambda tmp, size: lib.ms_mesh_component_filter(
     components.face_count.data_ptr(), components.num_components, min_faces, keep_largest, components.face_label.data_ptr(),
     num_faces, face_mask.data_ptr(), tmp, size, stream)
-  tmp, size = _tmp(call, device)
-  _lib.check(call(tmp.data_ptr(), ctypes.byref(size)), "remove_small_components")
+  _lib.run_with_scratch(call, device, "remove_small_components")
   cleaned = select_faces(mesh, face_mask)
   return (cleaned, components) if return_components else cleaned
 
@@ -194,8 +183,7 @@ def _normals(mesh: TriangleMesh, what: str, sums: bool) -> torch.Tensor:
   call = lambda tmp, size: lib.ms_mesh_vertex_normals(vertices.data_ptr(), faces.data_ptr(), num_vertices, num_faces,
                                                       out.data_ptr() if sums else None, None if sums else out.data_ptr(),
                                                       tmp, size, stream)
-  tmp, size = _tmp(call, device)
-  _lib.check(call(tmp.data_ptr(), ctypes.byref(size)), what)
+  _lib.run_with_scratch(call, device, what)
   return out
 
 

@@ -7,7 +7,6 @@ assignment, so a Lloyd run is bitwise reproducible.  1 <= D <= ``MAX_D``, 1 <= K
 """
 from __future__ import annotations
 
-import ctypes
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -70,22 +69,17 @@ def _check_sizes(n: int, d: int, k: int):
 def assign_scratch_bytes(n: int, d: int, k: int) -> int:
   """Bytes of scratch ``kmeans_assign_into`` needs (host arithmetic, no launch): the staged codebook and its norms."""
   _check_sizes(n, d, k)
-  nbytes = ctypes.c_size_t(0)
-  _lib.check(_lib.load().ms_kmeans_assign(None, n, d, None, k, None, None, None, ctypes.byref(nbytes), None), "kmeans_assign")
-  return int(nbytes.value)
+  lib = _lib.load()
+  return _lib.scratch_bytes(lambda tmp, size: lib.ms_kmeans_assign(None, n, d, None, k, None, None, tmp, size, None),
+                            "kmeans_assign")
 
 
 def update_scratch_bytes(n: int, d: int, k: int) -> int:
   """Bytes of scratch ``kmeans_update_into`` needs (host arithmetic, no launch): the sorted pairs and chunk sums."""
   _check_sizes(n, d, k)
-  nbytes = ctypes.c_size_t(0)
-  _lib.check(_lib.load().ms_kmeans_update(None, None, None, n, d, k, None, None, None, None, ctypes.byref(nbytes), None),
-             "kmeans_update")
-  return int(nbytes.value)
-
-
-def _scratch(nbytes: int, device) -> torch.Tensor:
-  return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device)
+  lib = _lib.load()
+  return _lib.scratch_bytes(
+    lambda tmp, size: lib.ms_kmeans_update(None, None, None, n, d, k, None, None, None, tmp, size, None), "kmeans_update")
 
 
 def kmeans_assign_into(x: torch.Tensor, codebook: torch.Tensor, out_index: torch.Tensor, out_dist2: Optional[torch.Tensor],
@@ -103,10 +97,10 @@ def kmeans_assign_into(x: torch.Tensor, codebook: torch.Tensor, out_index: torch
   _lib.require_gpu(x, codebook, out_index, out_dist2, scratch)
   _check_scratch(scratch, assign_scratch_bytes(n, d, k))
   _check_contiguous(x=x, codebook=codebook, out_index=out_index, out_dist2=out_dist2)
-  nbytes = ctypes.c_size_t(scratch.numel())
-  _lib.check(_lib.load().ms_kmeans_assign(_lib.ptr(x), n, d, _lib.ptr(codebook), k, _lib.ptr(out_index), _lib.ptr(out_dist2),
-                                          _lib.ptr(scratch), ctypes.byref(nbytes), _lib.current_stream(x.device)),
-             "kmeans_assign")
+  lib, stream = _lib.load(), _lib.current_stream(x.device)
+  _lib.run_in_scratch(lambda tmp, size: lib.ms_kmeans_assign(
+    _lib.ptr(x), n, d, _lib.ptr(codebook), k, _lib.ptr(out_index), _lib.ptr(out_dist2), tmp, size, stream),
+    scratch, "kmeans_assign")
 
 
 def kmeans_update_into(x: torch.Tensor, index: torch.Tensor, codebook: torch.Tensor, out_counts: torch.Tensor,
@@ -129,10 +123,10 @@ def kmeans_update_into(x: torch.Tensor, index: torch.Tensor, codebook: torch.Ten
   _lib.require_gpu(x, index, codebook, out_counts, scratch, weights, out_weight_sums)
   _check_scratch(scratch, update_scratch_bytes(n, d, k))
   _check_contiguous(x=x, index=index, codebook=codebook, out_counts=out_counts, weights=weights, out_weight_sums=out_weight_sums)
-  nbytes = ctypes.c_size_t(scratch.numel())
-  _lib.check(_lib.load().ms_kmeans_update(_lib.ptr(x), _lib.ptr(index), _lib.ptr(weights), n, d, k, _lib.ptr(codebook),
-                                          _lib.ptr(out_counts), _lib.ptr(out_weight_sums), _lib.ptr(scratch),
-                                          ctypes.byref(nbytes), _lib.current_stream(x.device)), "kmeans_update")
+  lib, stream = _lib.load(), _lib.current_stream(x.device)
+  _lib.run_in_scratch(lambda tmp, size: lib.ms_kmeans_update(
+    _lib.ptr(x), _lib.ptr(index), _lib.ptr(weights), n, d, k, _lib.ptr(codebook), _lib.ptr(out_counts),
+    _lib.ptr(out_weight_sums), tmp, size, stream), scratch, "kmeans_update")
 
 
 def kmeans_assign(x: torch.Tensor, codebook: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -145,7 +139,7 @@ def kmeans_assign(x: torch.Tensor, codebook: torch.Tensor) -> Tuple[torch.Tensor
   n, d = x.shape
   index = torch.empty((n,), dtype=torch.int32, device=x.device)
   dist2 = torch.empty((n,), dtype=torch.float32, device=x.device)
-  kmeans_assign_into(x, codebook, index, dist2, _scratch(assign_scratch_bytes(n, d, codebook.shape[0]), x.device))
+  kmeans_assign_into(x, codebook, index, dist2, _lib.scratch_block(assign_scratch_bytes(n, d, codebook.shape[0]), x.device))
   return index, dist2
 
 
@@ -163,7 +157,8 @@ def kmeans_update(x: torch.Tensor, index: torch.Tensor, codebook: torch.Tensor,
   k = codebook.shape[0]
   new = codebook.detach().clone().contiguous()
   counts = torch.empty((k,), dtype=torch.int32, device=x.device)
-  kmeans_update_into(x.detach().contiguous(), index.contiguous(), new, counts, _scratch(update_scratch_bytes(n, d, k), x.device),
+  kmeans_update_into(x.detach().contiguous(), index.contiguous(), new, counts,
+                     _lib.scratch_block(update_scratch_bytes(n, d, k), x.device),
                      None if weights is None else weights.detach().contiguous())
   return new, counts
 
@@ -206,8 +201,8 @@ def kmeans(x: torch.Tensor, k: int, iterations: int = 10, weights: Optional[torc
   index = torch.empty((n,), dtype=torch.int32, device=x.device)
   dist2 = torch.empty((n,), dtype=torch.float32, device=x.device)
   counts = torch.zeros((k,), dtype=torch.int32, device=x.device)
-  assign_scratch = _scratch(assign_scratch_bytes(n, d, k), x.device)
-  update_scratch = _scratch(update_scratch_bytes(n, d, k), x.device)
+  assign_scratch = _lib.scratch_block(assign_scratch_bytes(n, d, k), x.device)
+  update_scratch = _lib.scratch_block(update_scratch_bytes(n, d, k), x.device)
   for _ in range(iterations):
     kmeans_assign_into(x, codebook, index, None, assign_scratch)
     kmeans_update_into(x, index, codebook, counts, update_scratch, weights)

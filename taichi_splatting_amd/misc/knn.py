@@ -73,9 +73,8 @@ def morton_order(points: torch.Tensor) -> torch.Tensor:
 
 def scratch_bytes(n: int) -> int:
   """Bytes of scratch ``ms_knn_points`` needs for n points (host arithmetic, no launch)."""
-  nbytes = ctypes.c_size_t(0)
-  _lib.check(_lib.load().ms_knn_points(None, None, n, 1, None, None, None, None, ctypes.byref(nbytes), None), "knn")
-  return int(nbytes.value)
+  lib = _lib.load()
+  return _lib.scratch_bytes(lambda tmp, size: lib.ms_knn_points(None, None, n, 1, None, None, None, tmp, size, None), "knn")
 
 
 def knn_into(points: torch.Tensor, order: torch.Tensor, k: int, out_dist2: torch.Tensor, out_index: Optional[torch.Tensor],
@@ -92,10 +91,10 @@ def knn_into(points: torch.Tensor, order: torch.Tensor, k: int, out_dist2: torch
   assert out_index is None or (out_index.dtype == torch.int32 and out_index.shape == (n, k))
   assert stats is None or (stats.dtype == torch.int64 and stats.shape == (2,))
   assert scratch.dtype == torch.uint8
-  nbytes = ctypes.c_size_t(scratch.numel())
-  _lib.check(_lib.load().ms_knn_points(_lib.ptr(points), _lib.ptr(order), n, k, _lib.ptr(out_dist2), _lib.ptr(out_index),
-                                       _lib.ptr(stats), _lib.ptr(scratch), ctypes.byref(nbytes),
-                                       _lib.current_stream(points.device)), "knn")
+  lib, stream = _lib.load(), _lib.current_stream(points.device)
+  _lib.run_in_scratch(lambda tmp, size: lib.ms_knn_points(
+    _lib.ptr(points), _lib.ptr(order), n, k, _lib.ptr(out_dist2), _lib.ptr(out_index), _lib.ptr(stats), tmp, size, stream),
+    scratch, "knn")
 
 
 def knn(points: torch.Tensor, k: int = 3, *, order: Optional[torch.Tensor] = None,

@@ -61,17 +61,14 @@ def plan_densify(prune_mask: torch.Tensor, split_mask: torch.Tensor, children: i
   prune, split = _mask_bytes(prune_mask, n, 'prune_mask'), _mask_bytes(split_mask, n, 'split_mask')
   lib, stream = _lib.load(), _lib.current_stream(device)
 
-  tmp_bytes = ctypes.c_size_t(0)
-  _lib.check(lib.ms_densify_plan(None, None, n, int(children), None, None, None, None, ctypes.byref(tmp_bytes), None),
-             "densify plan")
   scan = torch.empty((2 * n + 1,), dtype=torch.int32, device=device)
-  tmp = torch.empty((max(tmp_bytes.value, 1),), dtype=torch.uint8, device=device)
   counts = torch.empty((4,), dtype=torch.int32, device=device)
   if device not in _pinned_counts:
     _pinned_counts[device] = torch.zeros((4,), dtype=torch.int32).pin_memory()
   host = _pinned_counts[device]
-  _lib.check(lib.ms_densify_plan(prune.data_ptr(), split.data_ptr(), n, int(children), scan.data_ptr(), counts.data_ptr(),
-                                 host.data_ptr(), tmp.data_ptr(), ctypes.byref(tmp_bytes), stream), "densify plan")
+  _lib.run_with_scratch(lambda tmp, size: lib.ms_densify_plan(
+    prune.data_ptr(), split.data_ptr(), n, int(children), scan.data_ptr(), counts.data_ptr(), host.data_ptr(), tmp, size,
+    stream), device, "densify plan")
   torch.cuda.current_stream(device).synchronize()
   n_kept, n_split, n_out, n_seen = (int(x) for x in host.tolist())
   assert n_seen == n and n_out == n_kept + n_split * children, "densify plan: inconsistent counts"

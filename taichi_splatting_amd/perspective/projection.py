@@ -7,7 +7,6 @@ instead of Taichi autodiff.
 """
 from __future__ import annotations
 
-import ctypes
 from numbers import Integral
 from typing import Tuple
 
@@ -50,11 +49,7 @@ def _project_forward(position, log_scaling, rotation, alpha_logit, T_camera_worl
     return points_full, depth_full.unsqueeze(1), empty_idx, depth_full.unsqueeze(1)
 
   scan = torch.empty((n + 1,), dtype=torch.int32, device=device)
-  nbytes = ctypes.c_size_t(0)
-  _lib.check(lib.ms_exclusive_scan_i32(None, n, None, None, None, ctypes.byref(nbytes), stream), "project_to_image")
-  tmp = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=device)
-  _lib.check(lib.ms_exclusive_scan_i32(flags.data_ptr(), n, scan.data_ptr(), None, tmp.data_ptr(),
-                                       ctypes.byref(nbytes), stream), "project_to_image")
+  _lib.exclusive_scan(flags.data_ptr(), n, scan.data_ptr(), device, "project_to_image")
   v = int(scan[n].item())   # host sync: V sizes the outputs (the reference syncs in torch.nonzero)
 
   if v == n and not with_ndc:

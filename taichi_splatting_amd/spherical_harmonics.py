@@ -156,11 +156,18 @@ def make_coded_sh_plan(sh_index: torch.Tensor, k: int) -> CodedSHPlan:
                      chunk_begin=i32(chunk_begin), chunk_off=i32(chunk_off), num_chunks=num_chunks, k=k)
 
 
+def _coded_bwd_call(plan: CodedSHPlan, degree: int, positions, cam, out, g_out, g_dc, g_codebook):
+  """``call(tmp_ptr, size_ref)`` of ms_sh_coded_bwd for the scratch helpers of ``_lib``"""
+  lib, stream = _lib.load(), None if out is None else _lib.current_stream(out.device)
+  return lambda tmp, size: lib.ms_sh_coded_bwd(
+    _lib.ptr(positions), _lib.ptr(cam), _lib.ptr(out), _lib.ptr(g_out), _lib.ptr(plan.rank), _lib.ptr(plan.chunk_begin),
+    _lib.ptr(plan.chunk_off), plan.num_chunks, plan.n, plan.k, degree, _lib.ptr(g_dc), _lib.ptr(g_codebook), tmp, size,
+    stream)
+
+
 def _coded_bwd(plan: CodedSHPlan, degree: int, positions, cam, out, g_out, g_dc, g_codebook, tmp, nbytes):
-  return _lib.load().ms_sh_coded_bwd(_lib.ptr(positions), _lib.ptr(cam), _lib.ptr(out), _lib.ptr(g_out), _lib.ptr(plan.rank),
-                                     _lib.ptr(plan.chunk_begin), _lib.ptr(plan.chunk_off), plan.num_chunks, plan.n, plan.k,
-                                     degree, _lib.ptr(g_dc), _lib.ptr(g_codebook), _lib.ptr(tmp), ctypes.byref(nbytes),
-                                     None if out is None else _lib.current_stream(out.device))
+  """The bare call on a block (uint8 tensor or None) and a ``c_size_t`` of the caller's; returns the code."""
+  return _coded_bwd_call(plan, degree, positions, cam, out, g_out, g_dc, g_codebook)(_lib.ptr(tmp), ctypes.byref(nbytes))
 
 
 class _CodedSHFunction(torch.autograd.Function):
@@ -191,12 +198,10 @@ class _CodedSHFunction(torch.autograd.Function):
     # every row is written, the rows of codes without members as zeros: no zero fill
     g_codebook = torch.empty(ctx.codebook_shape, dtype=torch.float32, device=out.device) if need_codebook else None
     if degree not in plan._scratch_bytes:
-      nbytes = ctypes.c_size_t(0)
-      _lib.check(_coded_bwd(plan, degree, None, None, None, None, None, None, None, nbytes), "evaluate_sh_coded backward")
-      plan._scratch_bytes[degree] = int(nbytes.value)
-    tmp = torch.empty((max(plan._scratch_bytes[degree], 1),), dtype=torch.uint8, device=out.device)
-    nbytes = ctypes.c_size_t(tmp.numel())
-    _lib.check(_coded_bwd(plan, degree, points, cam, out, g_out, g_dc, g_codebook, tmp, nbytes), "evaluate_sh_coded backward")
+      plan._scratch_bytes[degree] = _lib.scratch_bytes(_coded_bwd_call(plan, degree, None, None, None, None, None, None),
+                                                       "evaluate_sh_coded backward")
+    _lib.run_in_scratch(_coded_bwd_call(plan, degree, points, cam, out, g_out, g_dc, g_codebook),
+                        _lib.scratch_block(plan._scratch_bytes[degree], out.device), "evaluate_sh_coded backward")
     return g_dc, g_codebook, None, None, None, None
 
 

@@ -1,6 +1,6 @@
 """Stand-alone timing of ms_radix_sort_pairs on the two sorts of a config D frame (development tool):
 the K = 12.76 M (tile id, point) pairs on 14 bits and the V = 6 M (depth, point) pairs on 32 bits."""
-import sys, time, torch, ctypes
+import sys, time, torch
 sys.path.insert(0, '.')
 from taichi_splatting_amd import _lib
 lib = _lib.load()
@@ -13,12 +13,11 @@ for n, bits in CASES:
   keys = torch.randint(0, 2 ** min(bits, 31) - 1, (n,), dtype=torch.int32, device=dev)
   vals = torch.arange(n, dtype=torch.int32, device=dev)
   ko, vo = torch.empty_like(keys), torch.empty_like(vals)
-  nb = ctypes.c_size_t(0)
-  lib.ms_radix_sort_pairs(None, None, None, None, n, 4, 0, bits, None, ctypes.byref(nb), None)
-  tmp = torch.empty(nb.value, dtype=torch.uint8, device=dev)
   st = _lib.current_stream(dev)
+  sort = lambda tmp, size: lib.ms_radix_sort_pairs(keys.data_ptr(), vals.data_ptr(), ko.data_ptr(), vo.data_ptr(), n, 4, 0, bits, tmp, size, st)
+  block = _lib.scratch_block(_lib.scratch_bytes(sort, "sort"), dev)
   def run():
-    _lib.check(lib.ms_radix_sort_pairs(keys.data_ptr(), vals.data_ptr(), ko.data_ptr(), vo.data_ptr(), n, 4, 0, bits, tmp.data_ptr(), ctypes.byref(nb), st), "sort")
+    _lib.run_in_scratch(sort, block, "sort")
   for _ in range(5): run()
   torch.cuda.synchronize(); t0 = time.perf_counter()
   for _ in range(50): run()

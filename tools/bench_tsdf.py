@@ -160,10 +160,10 @@ def bench_extract(n, size, rounds, warmup, device):
   word = torch.empty((samples,), dtype=torch.int32, device=device)
   vscan = torch.empty((samples + 1,), dtype=torch.int32, device=device)
   tscan = torch.empty((samples + 1,), dtype=torch.int32, device=device)
-  need = ctypes.c_size_t(0)
   stream = _lib.current_stream(volume.device)
-  _lib.check(lib.ms_exclusive_scan_i32(None, samples, None, None, None, ctypes.byref(need), stream), "scan")
-  tmp = torch.empty((need.value,), dtype=torch.uint8, device=device)
+  scan_call = lambda scan: lambda tmp, size: lib.ms_exclusive_scan_i32(
+    scan.data_ptr(), samples, scan.data_ptr(), None, tmp, size, stream)
+  tmp = _lib.scratch_block(_lib.scratch_bytes(scan_call(vscan), "scan"), device)
   origin_c = (ctypes.c_double * 3)(*origin)
 
   def classify():
@@ -172,8 +172,7 @@ def bench_extract(n, size, rounds, warmup, device):
 
   def scans():
     for scan in (vscan, tscan):
-      _lib.check(lib.ms_exclusive_scan_i32(scan.data_ptr(), samples, scan.data_ptr(), None, tmp.data_ptr(), ctypes.byref(need),
-                                           stream), "scan")
+      _lib.run_in_scratch(scan_call(scan), tmp, "scan")
 
   for label in ('analytic sphere', 'fused sphere frames'):
     volume.reset()
