@@ -1183,6 +1183,95 @@ int ms_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t 
                            float* out_sums /* may be NULL */, float* out_normals /* may be NULL */, void* tmp,
                            size_t* tmp_bytes, void* stream);
 
+/* ---- Mesh simplification: vertex clustering with a quadric-error representative (csrc/mesh_simplify.hip; an addition) ---
+ * Rossignac & Borrel's clustering on a uniform grid with Lindstrom's (SIGGRAPH 2000) quadric placement per cell: one
+ * output vertex per occupied cell, the faces whose three corners fall into three different cells.  A sort, two scans and
+ * a per-cluster reduction; no float atomics; two runs give bitwise-equal outputs.  Meshes are as above.  NO entry point
+ * here takes a scratch block: every array is the caller's, and the caller runs ms_radix_sort_pairs (stable),
+ * ms_exclusive_scan_i32, ms_find_ranges and ms_mesh_select_plan / ms_mesh_select_gather between the calls, in the order
+ * the functions are declared below.  Output sizes depend on the data (two host reads: (K, status), then the selection's),
+ * so the sequence does not capture into a graph.
+ *
+ * CELL RULE.  cell(p) = floor((p - origin) / cell_size) per axis IN FLOAT32: one IEEE subtraction, one correctly rounded
+ * division, one floor (numpy float32 reproduces it bit for bit).  origin is 3 float32 ON THE DEVICE, cell_size a finite
+ * positive float32.  A cell index lies in 0 .. MS_MESH_SIMPLIFY_MAX_CELL = 2^21 - 1 per axis; the key of a cell is
+ * z << 42 | y << 21 | x.  Only vertices a face references are clustered: the others get the key 2^64 - 1, which sorts
+ * last, and cluster -1.  status (1 int32, device) receives 0 or a sum of MS_MESH_BAD_INDEX (a face index outside
+ * 0 .. V - 1; nothing is read or written through it), MS_MESH_NOT_FINITE (a referenced vertex with a NaN or an infinity)
+ * and MS_MESH_CELL_RANGE (a referenced, finite vertex whose cell index leaves the range, or is no number because origin
+ * is none); the caller must stop at a non-zero status.  head (2 int32, device) is poisoned to (-1, -1) by
+ * ms_mesh_simplify_keys and receives (K, status) from ms_mesh_simplify_clusters.
+ *
+ * ORDER RULE.  Clusters — and so output vertices — are in ascending key order; the members of a cluster are in ascending
+ * vertex index (the sort is stable); output faces keep the input order.
+ *
+ * FACE RULE.  A face is rewritten to its corners' clusters; it is dropped when two of them are equal, otherwise rotated
+ * so that its smallest index comes first (the orientation stays).  Of faces with the same rotated triple the one with the
+ * lowest input index survives; a pair with opposite orientation is not a duplicate.  Construction: a stable sort of
+ * (third index, face), ms_mesh_simplify_pair_keys in that order, a stable sort of (first << shift | second, face) with
+ * 2^shift > K - 1: equal triples are then adjacent in ascending face index, and ms_mesh_simplify_dedup clears keep[f] of a
+ * face whose triple equals its predecessor's.  new_faces holds (0, 0, 0) for a dropped face.  Clusters left without a
+ * face go in the selection's compaction (SELECTION ORDER), and ms_mesh_simplify_map composes the two maps:
+ * vertex_map[v] = the output vertex of v, -1 for a vertex no face references or whose cluster lost all its faces.
+ *
+ * PLACEMENT RULE (ms_mesh_simplify_place).  xm = the float64 mean of the cluster's member positions.
+ * MS_MESH_SIMPLIFY_MEAN places the vertex at xm, rounded to float32 once.  MS_MESH_SIMPLIFY_QUADRIC: over every corner
+ * (f, k) whose vertex is in the cluster (a face counts once per such corner), with (a, b, c) the positions of face f,
+ * m = (b - a) x (c - a) and d = -m . (a - xm) in float64 on the float32 positions: A = sum m m^T, r = sum d m, and
+ * x = xm - (A + lambda I)^-1 r with lambda = regularisation trace(A) / 3 — the minimiser of the summed squared
+ * area-weighted plane distances plus a pull of relative weight `regularisation` towards the mean; a closed-form 3 x 3
+ * symmetric positive definite solve (adjugate over determinant) of condition number <= 1 + 3 / regularisation.  x is
+ * rounded to float32 once and accepted only if cell(x), by the CELL RULE, is the cluster's own cell; otherwise, or when
+ * trace(A) == 0 or x is not finite, the vertex is xm rounded once, under the same test; failing that too it is the member
+ * with the lowest index, bit for bit.  INVARIANT: every output vertex lies in its own cluster's cell under the CELL RULE,
+ * so simplifying the result again with the same origin and cell_size returns the same faces.  Summation order: 16 lanes
+ * share a cluster, lane j adds the entries j, j + 16, .. of the run (members in ascending vertex index, corners in
+ * ascending corner index 3 f + k) and the 16 partials meet in a fixed butterfly (1, 2, 4, 8 lanes apart): the order
+ * depends on the run's length alone.  out_colours (when colours is given) = the float64 mean of the members' colours,
+ * rounded once; normals are not carried.  out_choice (K uint8, may be NULL) = which of the three the cluster took. */
+#define MS_MESH_NOT_FINITE 4
+#define MS_MESH_CELL_RANGE 8
+#define MS_MESH_SIMPLIFY_MAX_CELL 2097151
+#define MS_MESH_SIMPLIFY_QUADRIC 0
+#define MS_MESH_SIMPLIFY_MEAN 1
+#define MS_MESH_SIMPLIFY_MEMBER 2
+/* origin (3 float32, device) = the smallest FINITE coordinate of all V vertices per axis — the default origin: the lowest
+ * vertex then falls into cell 0; +infinity for an axis without a finite value, (0, 0, 0) for V = 0.  -0 counts as below
+ * +0, so the bits of the result are defined as well.  Integer atomics on the float's bits, chosen by the sign bit (a
+ * minimum in a total order does not depend on the order of its operands). */
+int ms_mesh_simplify_origin(const float* vertices, int64_t num_vertices, float* origin, void* stream);
+/* referenced (V) int32 is scratch of the call; keys (V) u64 and values (V) = 0 .. V - 1 are the pairs to sort on bits 0 .. 64 */
+int ms_mesh_simplify_keys(const float* vertices, const int32_t* faces, int64_t num_vertices, int64_t num_faces,
+                          const float* origin, float cell_size, int32_t* referenced, uint64_t* keys, int32_t* values,
+                          int32_t* status, int32_t* head, void* stream);
+/* head_flag (V + 1) int32: [i] = the sorted key i opens a cluster; the caller scans it in place ([V] = K) */
+int ms_mesh_simplify_heads(const uint64_t* sorted_keys, int64_t num_vertices, int32_t* head_flag, void* stream);
+/* vertex_cluster (V) int32; member_begin (V + 1) int32, of which [0 .. K] are written: cluster c owns the sorted entries
+ * member_begin[c] .. member_begin[c + 1] - 1 */
+int ms_mesh_simplify_clusters(const uint64_t* sorted_keys, const int32_t* sorted_vertices, const int32_t* head_scan,
+                              int64_t num_vertices, int32_t* vertex_cluster, int32_t* member_begin, const int32_t* status,
+                              int32_t* head, void* stream);
+/* keys, values (3 T): (cluster, corner) pairs, to sort on the low bits that hold K; then ms_find_ranges over K clusters */
+int ms_mesh_simplify_corner_keys(const int32_t* faces, int64_t num_vertices, int64_t num_faces, const int32_t* vertex_cluster,
+                                 int64_t num_clusters, uint32_t* keys, int32_t* values, void* stream);
+/* corner_ranges (K, 2) and sorted_corners (3 T) may be NULL with MS_MESH_SIMPLIFY_MEAN */
+int ms_mesh_simplify_place(const float* vertices, const float* colours /* may be NULL */, const int32_t* faces,
+                           int64_t num_vertices, int64_t num_faces, const float* origin, float cell_size,
+                           double regularisation, int placement, const uint64_t* sorted_keys, const int32_t* sorted_vertices,
+                           const int32_t* member_begin, int64_t num_clusters, const int32_t* corner_ranges,
+                           const int32_t* sorted_corners, float* out_vertices, float* out_colours, uint8_t* out_choice,
+                           void* stream);
+/* new_faces (T, 3), third_keys (T), values (T) = 0 .. T - 1, keep (T) uint8 */
+int ms_mesh_simplify_faces(const int32_t* faces, int64_t num_vertices, int64_t num_faces, const int32_t* vertex_cluster,
+                           int64_t num_clusters, int32_t* new_faces, uint32_t* third_keys, int32_t* values, uint8_t* keep,
+                           void* stream);
+int ms_mesh_simplify_pair_keys(const int32_t* new_faces, const int32_t* order, int64_t num_faces, int shift,
+                               uint64_t* pair_keys, void* stream);
+int ms_mesh_simplify_dedup(const int32_t* new_faces, const int32_t* order, int64_t num_faces, uint8_t* keep, void* stream);
+/* cluster_scan (K + 1): vertex_scan of ms_mesh_select_plan over the K clusters */
+int ms_mesh_simplify_map(const int32_t* vertex_cluster, int64_t num_vertices, const int32_t* cluster_scan,
+                         int64_t num_clusters, int32_t* vertex_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

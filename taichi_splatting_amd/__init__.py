@@ -30,7 +30,7 @@ from .appearance import apply_bilateral_grid, BilateralGrids, identity_bilateral
 from .geometry import gaussian_normals, render_geometry, GeometryImages, normal_consistency_loss, normal_consistency
 from .fusion import TSDFVolume, TriangleMesh, save_mesh_ply, fuse_scene
 from .mesh import (MeshComponents, mesh_components, select_faces, remove_small_components, vertex_normals,
-                   vertex_normal_sums, with_vertex_normals)
+                   vertex_normal_sums, with_vertex_normals, simplify_mesh)
 
 __version__ = '0.5.1'       # = MS_VERSION 501 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -52,7 +52,7 @@ __all__ = [
   'gaussian_normals', 'render_geometry', 'GeometryImages', 'normal_consistency_loss', 'normal_consistency',
   'TSDFVolume', 'TriangleMesh', 'save_mesh_ply', 'fuse_scene',
   'MeshComponents', 'mesh_components', 'select_faces', 'remove_small_components', 'vertex_normals', 'vertex_normal_sums',
-  'with_vertex_normals',
+  'with_vertex_normals', 'simplify_mesh',
 ]
 
 

@@ -42,6 +42,9 @@ TSDF_RUN = 4                      # MS_TSDF_RUN: consecutive samples a lane of m
 TSDF_CAMERA_CHUNK = 64            # MS_TSDF_CAMERA_CHUNK: cameras a wave of ms_tsdf_integrate culls per ballot
 MESH_MAX_VERTICES = MESH_MAX_CORNERS = 2 ** 31 - 1   # MS_MESH_MAX_VERTICES / MS_MESH_MAX_CORNERS
 MESH_BAD_INDEX, MESH_GAVE_UP = 1, 2               # MS_MESH_BAD_INDEX / MS_MESH_GAVE_UP (status bits of the mesh calls)
+MESH_NOT_FINITE, MESH_CELL_RANGE = 4, 8           # MS_MESH_NOT_FINITE / MS_MESH_CELL_RANGE (status bits of ms_mesh_simplify_keys)
+MESH_SIMPLIFY_MAX_CELL = 2 ** 21 - 1              # MS_MESH_SIMPLIFY_MAX_CELL
+MESH_SIMPLIFY_QUADRIC, MESH_SIMPLIFY_MEAN, MESH_SIMPLIFY_MEMBER = range(3)   # MS_MESH_SIMPLIFY_*: placement / out_choice
 RELOCATE_COPY, RELOCATE_ZERO_TOUCHED, RELOCATE_INHERIT, RELOCATE_OPACITY, RELOCATE_SCALE = range(5)   # MS_RELOCATE_*
 
 _lib: Optional[ctypes.CDLL] = None
@@ -244,6 +247,17 @@ SIGNATURES = {
   'ms_mesh_select_plan': (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 4 + [POINTER(c_size_t), c_void_p]),
   'ms_mesh_select_gather': (c_int, [c_void_p] * 5 + [c_int64, c_int64] + [c_void_p] * 7),
   'ms_mesh_vertex_normals': (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 3 + [POINTER(c_size_t), c_void_p]),
+  'ms_mesh_simplify_origin': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+  'ms_mesh_simplify_keys': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float] + [c_void_p] * 6),
+  'ms_mesh_simplify_heads': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+  'ms_mesh_simplify_clusters': (c_int, [c_void_p] * 3 + [c_int64] + [c_void_p] * 5),
+  'ms_mesh_simplify_corner_keys': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64] + [c_void_p] * 3),
+  'ms_mesh_simplify_place': (c_int, [c_void_p] * 3 + [c_int64, c_int64, c_void_p, c_float, c_double, c_int] + [c_void_p] * 3
+                             + [c_int64] + [c_void_p] * 6),
+  'ms_mesh_simplify_faces': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64] + [c_void_p] * 5),
+  'ms_mesh_simplify_pair_keys': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+  'ms_mesh_simplify_dedup': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+  'ms_mesh_simplify_map': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

@@ -9,7 +9,7 @@ float32 only, detached, no autograd; there is no torch fallback and CPU tensors 
 reads the two scan totals on the host once, to size its outputs, and therefore does not capture.  No kernel uses an
 atomic: both calls are bitwise reproducible.
 
-Out of scope: sparse or hashed volumes, float64, gradients, median depth, mesh simplification, marching cubes,
+Out of scope: sparse or hashed volumes, float64, gradients, median depth, marching cubes,
 tile-row strips and more than one GPU.
 """
 from __future__ import annotations

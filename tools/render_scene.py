@@ -12,7 +12,8 @@ gaussians and tile overlaps; ms per frame is the median over the views after one
     python tools/render_scene.py scene.ply [--size W H] [--views K] [--out DIR] [--sh-degree d] [--transform "x 90 0.5"]
                                            [--coverage] [--sh-codes K [--coded]]
                                            [--mesh out.ply --voxel-size s [--bounds x0 y0 z0 x1 y1 z1]
-                                            [--min-component-faces N] [--keep-components K] [--mesh-normals]]
+                                            [--min-component-faces N] [--keep-components K] [--mesh-cell-size s]
+                                            [--mesh-normals]]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 --transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
@@ -34,6 +35,9 @@ vertices from the orbit centre (for a scene that is a sphere about it, the radia
 triangles and --keep-components K (default: all) keeps only the K largest (mesh.remove_small_components, on the device);
 --mesh-normals adds area-weighted vertex normals (nx ny nz) to the written file.  With either of the first two the JSON
 line also gains the counts before cleaning, the number of components found and the time of the clean-up.
+--mesh-cell-size s simplifies the mesh by vertex clustering on a grid of side s with quadric placement
+(mesh.simplify_mesh, on the device) after the component removal and before --mesh-normals; the JSON line gains the vertex
+and triangle counts before and after and the time of the call.
 --coded (with --sh-codes) also renders the quantised scene straight from its codebook (render_compressed: no decoded
 feature tensor) and adds the PSNR of that render against the decoded one (null when they are identical) and the median
 frame time of both, after one warm-up pass each.
@@ -119,7 +123,7 @@ def coverage_report(gaussians, cameras, config):
 
 
 def mesh_report(gaussians, cameras, config, path, voxel_size, bounds, min_component_faces=1, keep_components=None,
-                mesh_normals=False):
+                mesh_normals=False, mesh_cell_size=None):
   """fuse_scene over ``cameras`` + extract_mesh + save_mesh_ply: dims, counts, seconds, vertex distances from the orbit centre"""
   from taichi_splatting_amd import TSDFVolume, fuse_scene, save_mesh_ply
   if bounds is None:
@@ -148,6 +152,16 @@ def mesh_report(gaussians, cameras, config, path, voxel_size, bounds, min_compon
     torch.cuda.synchronize()
     cleaning = dict(vertices_before=before[0], triangles_before=before[1], components=components.num_components,
                     clean_s=round(time.perf_counter() - clean_start, 4))
+  simplification = None
+  if mesh_cell_size is not None:
+    from taichi_splatting_amd import simplify_mesh
+    before = (int(mesh.vertices.shape[0]), int(mesh.faces.shape[0]))
+    simplify_start = time.perf_counter()
+    mesh = simplify_mesh(mesh, mesh_cell_size)
+    torch.cuda.synchronize()
+    simplification = dict(cell_size=mesh_cell_size, vertices_before=before[0], triangles_before=before[1],
+                          vertices_after=int(mesh.vertices.shape[0]), triangles_after=int(mesh.faces.shape[0]),
+                          simplify_s=round(time.perf_counter() - simplify_start, 4))
   if mesh_normals:
     from taichi_splatting_amd import with_vertex_normals
     mesh = with_vertex_normals(mesh)
@@ -159,6 +173,8 @@ def mesh_report(gaussians, cameras, config, path, voxel_size, bounds, min_compon
                 distance_from_centre=[round(float(x), 6) for x in (distance.median(), distance.min(), distance.max())])
   if cleaning is not None:
     report.update(cleaning)
+  if simplification is not None:
+    report['simplification'] = simplification
   if mesh_normals:
     report['normals'] = True
   print(f"mesh: {dims[0]} x {dims[1]} x {dims[2]} samples of {voxel_size}; {report['vertices']} vertices, {report['triangles']} "
@@ -252,14 +268,17 @@ def main():
                  help="drop the connected components of the --mesh mesh with fewer than N triangles (default 1: none)")
   p.add_argument('--keep-components', type=int, default=None, metavar='K',
                  help="keep only the K largest components of the --mesh mesh (default: all)")
+  p.add_argument('--mesh-cell-size', type=float, default=None, metavar='s',
+                 help="simplify the --mesh mesh by vertex clustering on a grid of side s (default: not simplified)")
   p.add_argument('--mesh-normals', action='store_true', help="write area-weighted vertex normals into the --mesh file")
   p.add_argument('--bounds', type=float, nargs=6, default=None, metavar=('x0', 'y0', 'z0', 'x1', 'y1', 'z1'),
                  help="box of the --mesh volume (default: the box of the gaussians' positions)")
   args = p.parse_args()
   if (args.mesh is None) != (args.voxel_size is None) or (args.bounds is not None and args.mesh is None):
     sys.exit("render_scene: --mesh and --voxel-size go together (--bounds is optional with them)")
-  if args.mesh is None and (args.min_component_faces != 1 or args.keep_components is not None or args.mesh_normals):
-    sys.exit("render_scene: --min-component-faces, --keep-components and --mesh-normals need --mesh")
+  if args.mesh is None and (args.min_component_faces != 1 or args.keep_components is not None or args.mesh_normals
+                            or args.mesh_cell_size is not None):
+    sys.exit("render_scene: --min-component-faces, --keep-components, --mesh-cell-size and --mesh-normals need --mesh")
   if args.min_component_faces < 1 or (args.keep_components is not None and args.keep_components < 1):
     sys.exit("render_scene: --min-component-faces and --keep-components must be at least 1")
   if args.voxel_size is not None and not args.voxel_size > 0:
@@ -331,7 +350,7 @@ def main():
   if args.mesh is not None:
     try:
       mesh = mesh_report(gaussians, cameras, config, args.mesh, args.voxel_size, args.bounds, args.min_component_faces,
-                         args.keep_components, args.mesh_normals)
+                         args.keep_components, args.mesh_normals, args.mesh_cell_size)
     except ValueError as e:
       sys.exit(f"render_scene: --mesh: {e}")
   print(json.dumps(dict(
