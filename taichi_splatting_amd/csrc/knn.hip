@@ -38,14 +38,9 @@ __device__ __forceinline__ float knn_dist2(float dx, float dy, float dz) { retur
 // component of the distance from the interval [lo, hi] to the interval [a, b] (a == b: a point); 0 when they overlap
 __device__ __forceinline__ float knn_gap(float lo, float hi, float a, float b) { return fmaxf(fmaxf(lo - b, a - hi), 0.0f); }
 
-__device__ __forceinline__ float wave_min_all(float v) {
-  for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max_all(float v) {
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
+// the operators of the box reductions (wave_all)
+struct KnnMin { __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); } };
+struct KnnMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
 
 struct KnnScratch {
   size_t rows, lo, hi, total;
@@ -80,8 +75,8 @@ knn_gather_blocks_kernel(const float* __restrict__ points, const int32_t* __rest
   const int wave = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    lo[a] = wave_min_all(lo[a]);
-    hi[a] = wave_max_all(hi[a]);
+    lo[a] = wave_all(lo[a], KnnMin());
+    hi[a] = wave_all(hi[a], KnnMax());
     if (lane_id() == 0) {
       part[wave][a] = lo[a];
       part[wave][3 + a] = hi[a];
@@ -180,12 +175,12 @@ knn_search_kernel(const float4* __restrict__ rows, const float4* __restrict__ bl
 
   // the box of this wave's queries
   float wlo[3], whi[3];
-  wlo[0] = wave_min_all(active ? q.x : INFINITY);
-  wlo[1] = wave_min_all(active ? q.y : INFINITY);
-  wlo[2] = wave_min_all(active ? q.z : INFINITY);
-  whi[0] = wave_max_all(active ? q.x : -INFINITY);
-  whi[1] = wave_max_all(active ? q.y : -INFINITY);
-  whi[2] = wave_max_all(active ? q.z : -INFINITY);
+  wlo[0] = wave_all(active ? q.x : INFINITY, KnnMin());
+  wlo[1] = wave_all(active ? q.y : INFINITY, KnnMin());
+  wlo[2] = wave_all(active ? q.z : INFINITY, KnnMin());
+  whi[0] = wave_all(active ? q.x : -INFINITY, KnnMax());
+  whi[1] = wave_all(active ? q.y : -INFINITY, KnnMax());
+  whi[2] = wave_all(active ? q.z : -INFINITY, KnnMax());
 
   // the other blocks, 64 per step, outward from the own one along the curve: own chunk, +1, -1, +2, -2, ...
   const int chunks = (blocks + WAVE - 1) / WAVE, own_chunk = own / WAVE;
@@ -195,7 +190,7 @@ knn_search_kernel(const float4* __restrict__ rows, const float4* __restrict__ bl
     const int chunk = (t & 1) ? own_chunk + off : own_chunk - off;
     if (chunk < 0 || chunk >= chunks) continue;
     // candidates: the block's box against the wave's box and the wave's largest K-th best (each lane one block)
-    const float reach = wave_max_all(active ? best.d[K - 1] : -INFINITY);
+    const float reach = wave_all(active ? best.d[K - 1] : -INFINITY, KnnMax());
     const int b = chunk * WAVE + lane_id();
     bool candidate = false;
     if (b < blocks && b != own) {

@@ -113,7 +113,7 @@ __device__ __forceinline__ void emit_span(const ObbQuery& q, bool valid, int64_t
     int64_t o = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
     wave_walk_span(b, tile_size, row_begin, row_end, [&](bool hit, int tx, int ty) {
       const unsigned long long m = __ballot(hit);
-      if (hit) emit(o + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)), tx, ty, src);
+      if (hit) emit(o + lane_rank_mbcnt(m), tx, ty, src);
       o += __builtin_popcountll(m);
     });
   }

@@ -70,22 +70,6 @@ __device__ __forceinline__ bool simplify_in_range(int32_t a, int32_t b, int32_t 
 
 __device__ __forceinline__ bool simplify_finite(double v) { return v - v == 0.0; }
 
-// v of the lane the DPP control names; every lane of the wave is active where this is called
-template <int CTRL>
-__device__ __forceinline__ double simplify_dpp(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false),
-                          __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false));
-}
-// Sum over the 16 lanes of a DPP row, the same bits in every lane of the row.
-__device__ __forceinline__ double simplify_row_sum(double v) {
-  v += simplify_dpp<0xb1>(v);                       // quad_perm:[1,0,3,2]   lane ^ 1
-  v += simplify_dpp<0x4e>(v);                       // quad_perm:[2,3,0,1]   lane ^ 2
-  v += simplify_dpp<0x141>(v);                      // row_half_mirror       the other quad of the half
-  v += simplify_dpp<0x140>(v);                      // row_mirror            the other half of the row
-  return v;
-}
-
 // The default origin: the smallest finite coordinate per axis, under the total order in which -0 lies below +0
 // (simplify_below), so that the BITS of the result do not depend on any order either.  A lane walks a grid-stride run, the
 // wave combines, and lane 0 commits with INTEGER atomics on the float's bits, chosen by the SIGN BIT: a pattern without
@@ -111,11 +95,7 @@ simplify_origin_kernel(const float* __restrict__ vertices, int64_t num_vertices,
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    float x = low[k];
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float y = __shfl_xor(x, off, WAVE);
-      if (simplify_below(y, x)) x = y;
-    }
+    const float x = wave_all(low[k], [](float x, float y) { if (simplify_below(y, x)) x = y; return x; });
     // a wave that cannot lower the value it sees stays out: the stored value only ever falls in that order, so a commit
     // that is skipped would have changed nothing.  The load is a filter only; the atomics alone decide.
     const float seen = __hip_atomic_load(origin + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -243,13 +223,13 @@ simplify_place_kernel(const float* __restrict__ vertices, const float* __restric
       cb += (double)colours[(int64_t)v * 3 + 2];
     }
   }
-  sx = simplify_row_sum(sx);
-  sy = simplify_row_sum(sy);
-  sz = simplify_row_sum(sz);
+  sx = row_sum16(sx);
+  sy = row_sum16(sy);
+  sz = row_sum16(sz);
   if (colours) {                                                     // uniform over the launch
-    cr = simplify_row_sum(cr);
-    cg = simplify_row_sum(cg);
-    cb = simplify_row_sum(cb);
+    cr = row_sum16(cr);
+    cg = row_sum16(cg);
+    cb = row_sum16(cb);
   }
   const double members = (double)(end > begin ? end - begin : 1);
   const double mx = sx / members, my = sy / members, mz = sz / members;
@@ -287,15 +267,15 @@ simplify_place_kernel(const float* __restrict__ vertices, const float* __restric
       ry += d * ny;
       rz += d * nz;
     }
-    axx = simplify_row_sum(axx);
-    axy = simplify_row_sum(axy);
-    axz = simplify_row_sum(axz);
-    ayy = simplify_row_sum(ayy);
-    ayz = simplify_row_sum(ayz);
-    azz = simplify_row_sum(azz);
-    rx = simplify_row_sum(rx);
-    ry = simplify_row_sum(ry);
-    rz = simplify_row_sum(rz);
+    axx = row_sum16(axx);
+    axy = row_sum16(axy);
+    axz = row_sum16(axz);
+    ayy = row_sum16(ayy);
+    ayz = row_sum16(ayz);
+    azz = row_sum16(azz);
+    rx = row_sum16(rx);
+    ry = row_sum16(ry);
+    rz = row_sum16(rz);
   }
   if (!live || sub != 0 || end <= begin) return;                     // the reductions are over: one lane finishes the cluster
 

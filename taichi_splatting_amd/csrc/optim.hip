@@ -114,13 +114,6 @@ struct CommonArgs {
   int64_t m_count;
 };
 
-template <int LPP>
-__device__ __forceinline__ float group_sum(float x) {
-#pragma unroll
-  for (int off = LPP / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-
 template <int VEC> struct Piece;
 template <> struct Piece<1> {
   static __device__ __forceinline__ void load(const float* p, float* out) { out[0] = *p; }
@@ -223,7 +216,7 @@ __device__ __forceinline__ void update_point(const GroupArgs& a, const PointWord
     float norm = 0.f;
 #pragma unroll
     for (int e = 0; e < E; ++e) norm += g[e] * g[e];
-    norm = group_sum<LPP>(norm);
+    norm = group_all<LPP>(norm, [](float a, float b) { return a + b; });
     float v = 0.f;
     if (live) {
       v = lerp_t(b2w, a.v[idx], norm);

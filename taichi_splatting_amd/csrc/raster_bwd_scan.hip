@@ -484,7 +484,7 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
         const unsigned long long m = __ballot(hit);
         const int nhit = __builtin_popcountll(m);
         if (pcount + nhit > CAP) break;          // next pass (nhit <= 64 <= CAP: an empty list always takes the group)
-        const int ppos = pcount + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const int ppos = pcount + lane_rank_mbcnt(m);
         if (hit) s_plist[wave][ppos] = (uint16_t)j;
         pcount += nhit;
         r += 64;
@@ -516,7 +516,7 @@ raster_bwd_scan_kernel(const float* __restrict__ points, const float* __restrict
             const float rcx = (float)(patch_x + (q & 1) * 4) + 2.0f, rcy = (float)(patch_y + (q >> 1) * 4) + 2.0f;
             const bool hit = in && scan_rect_hit(q0, q1, rcx, rcy, 1.5f);
             const unsigned long long m = __ballot(hit);
-            const int pos = cnt[q] + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const int pos = cnt[q] + lane_rank_mbcnt(m);
             if (hit) s_list[wave][q][pos] = (uint8_t)ppos;
             cnt[q] += __builtin_popcountll(m);
           }

@@ -256,11 +256,6 @@ __device__ __forceinline__ bool patch_hit(const float4 c0, const float4 c1, floa
   return rect_hit(c0, c1, rcx, rcy, 3.5f);
 }
 
-template <int CTRL>
-__device__ __forceinline__ float add_dpp(float keep, float send) {
-  return keep + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(send), CTRL, 0xf, 0xf, true));
-}
-
 // index of the value whose total lane `lane` holds after wave_reduce16 (valid when (lane & 15) >= 12)
 __device__ __forceinline__ int butterfly_slot(int lane) {
   return 4 * (2 * (lane >> 5) + ((lane >> 4) & 1)) + (lane & 3);

@@ -257,7 +257,7 @@ raster_wide_bwd_kernel(const float* __restrict__ points, const float* __restrict
       const bool hit = lane < count && patch_hit(s_cull[2 * lane], s_cull[2 * lane + 1], rcx, rcy);
       unsigned long long m = __ballot(hit);
       const int n = __popcll(m);
-      if (hit) s_hit[wave][__popcll(m & ((1ull << lane) - 1ull))] = lane;
+      if (hit) s_hit[wave][lane_rank_popc(m)] = lane;
       wave_lds_fence();
 
       for (int g0 = 0; g0 < n; g0 += 32) {

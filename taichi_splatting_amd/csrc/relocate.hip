@@ -46,18 +46,9 @@ typedef uint32_t __attribute__((ext_vector_type(4), may_alias)) piece16;
 // Counting rows into one device word: a same-address atomic costs about 12 ns at the L2, so one per wave (94 K waves at
 // 6 M rows) would take longer than the kernel's work.  The draw and fresh kernels therefore run a bounded grid with a
 // grid-stride loop: a wave adds up the popcounts of its ballots (a scalar), the block adds its four waves in LDS and
-// commits ONE atomic, at most COUNT_BLOCKS per launch.  Every lane of the block must reach both calls.
+// commits ONE atomic (block_count_commit, wave.h), at most COUNT_BLOCKS per launch.  Every lane of the block must
+// reach both calls.
 constexpr int COUNT_BLOCKS = 2048;
-
-__device__ __forceinline__ void block_count_commit(uint32_t wave_total, int64_t* dst) {
-  __shared__ uint32_t totals[4];
-  if (lane_id() == 0) totals[threadIdx.x >> 6] = wave_total;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t t = totals[0] + totals[1] + totals[2] + totals[3];
-    if (t != 0) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)t);
-  }
-}
 
 __global__ void __launch_bounds__(256)
 relocate_weights_kernel(const float* __restrict__ alpha_logit, int64_t n, float threshold, int64_t* __restrict__ weights,
@@ -237,7 +228,7 @@ relocate_move_kernel(RelocArgs m) {
     row_of[threadIdx.x] = (uint8_t)threadIdx.x;
     touched = rows;
   } else if (e >= 0) {
-    const int at = before + __popcll(mask & ((1ull << lane_id()) - 1ull));
+    const int at = before + lane_rank_popc(mask);
     enc[at] = e;
     row_of[at] = (uint8_t)threadIdx.x;
   }

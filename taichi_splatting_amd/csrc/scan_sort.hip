@@ -22,30 +22,9 @@ namespace ms {
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
+constexpr int SCAN_WAVES = SCAN_THREADS / 64;
 
-// exclusive scan of one int per thread across a 256-thread block; returns the exclusive prefix,
-// *block_total receives the block sum (valid in all threads).
-__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /*>= 4 ints*/, int* block_total) {
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
-  if (lane == 63) lds[wave] = incl;
-  __syncthreads();
-  int wave_off = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < SCAN_THREADS / 64; ++w) {
-    const int s = lds[w];
-    if (w < wave) wave_off += s;
-    total += s;
-  }
-  __syncthreads();
-  *block_total = total;
-  return wave_off + incl - v;
-}
+// block scans: block_exclusive_sum<SCAN_WAVES> (wave.h), each followed by the barrier that frees its LDS words
 
 // a thread's SCAN_ITEMS consecutive ints: four 128-bit loads when the tile is complete and aligned
 __device__ __forceinline__ void load_items(const int32_t* __restrict__ in, int64_t base, int64_t n, int (&vals)[SCAN_ITEMS]) {
@@ -83,7 +62,8 @@ scan_block_sums_kernel(const int32_t* __restrict__ in, int64_t n, int32_t* __res
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) s += items[k];
   int total;
-  block_exclusive_scan(s, lds, &total);
+  block_exclusive_sum<SCAN_WAVES>(s, lds, &total);
+  __syncthreads();
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -97,7 +77,8 @@ scan_spine_kernel(int32_t* __restrict__ block_sums, int64_t num_blocks, int32_t*
     const int64_t i = base + threadIdx.x;
     const int v = i < num_blocks ? block_sums[i] : 0;
     int total;
-    const int ex = block_exclusive_scan(v, lds, &total);
+    const int ex = block_exclusive_sum<SCAN_WAVES>(v, lds, &total);
+    __syncthreads();
     if (i < num_blocks) block_sums[i] = carry + ex;
     carry += total;
   }
@@ -119,7 +100,9 @@ scan_downsweep_kernel(const int32_t* __restrict__ in, int64_t n, const int32_t* 
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) s += vals[k];
   int total;
-  int prefix = block_exclusive_scan(s, lds, &total) + block_offsets[blockIdx.x];
+  const int ex = block_exclusive_sum<SCAN_WAVES>(s, lds, &total);
+  __syncthreads();
+  int prefix = ex + block_offsets[blockIdx.x];
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) {       // vals[k] <- exclusive prefix of item k
     const int v = vals[k];
@@ -142,7 +125,8 @@ scan_downsweep_self_kernel(const int32_t* __restrict__ in, int64_t n, const int3
   int before = 0;
   for (int j = threadIdx.x; j < (int)blockIdx.x; j += SCAN_THREADS) before += block_sums[j];
   int block_prefix;
-  block_exclusive_scan(before, lds, &block_prefix);
+  block_exclusive_sum<SCAN_WAVES>(before, lds, &block_prefix);
+  __syncthreads();
 
   const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
   int vals[SCAN_ITEMS];
@@ -151,7 +135,8 @@ scan_downsweep_self_kernel(const int32_t* __restrict__ in, int64_t n, const int3
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) s += vals[k];
   int total;
-  int prefix = block_exclusive_scan(s, lds, &total) + block_prefix;
+  int prefix = block_exclusive_sum<SCAN_WAVES>(s, lds, &total) + block_prefix;
+  __syncthreads();
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) {       // vals[k] <- exclusive prefix of item k
     const int v = vals[k];
@@ -295,6 +280,7 @@ __device__ __forceinline__ void upsweep_block(const Source src, int64_t n, int s
   }
   if (VARY) {
     // one LDS atomic per wave, not per thread (256 atomics on one word are served one after the other: +18 us)
+    // the two butterflies share each step's lane address, so they stay one loop and not two wave_all calls
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) { v_or |= __shfl_xor(v_or, off); v_and &= __shfl_xor(v_and, off); }
     if (lane == 0) { atomicOr(&s_or, v_or); atomicAnd(&s_and, v_and); }
@@ -336,7 +322,8 @@ __device__ __forceinline__ void row_scan_body(int32_t* __restrict__ hist, int64_
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) s += vals[k];
     int total;
-    int prefix = carry + block_exclusive_scan(s, lds, &total);
+    int prefix = carry + block_exclusive_sum<SCAN_WAVES>(s, lds, &total);
+    __syncthreads();
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
       const int v = vals[k];
@@ -380,7 +367,6 @@ __device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT, typename S
 
   const int wave = threadIdx.x >> 6, lane = lane_id();
   const int64_t base = (int64_t)blockIdx.x * RS_TILE + (int64_t)wave * RS_WAVE_ITEMS + lane;
-  const unsigned long long lanes_below = (1ull << lane) - 1ull;
 
   using ValT = typename Source::value_type;
   KeyT k[RS_ROUNDS];
@@ -413,7 +399,7 @@ __device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT, typename S
       peers_hi &= ~((unsigned)(bal >> 32) ^ (unsigned)m);
     }
     const unsigned long long peers = ((unsigned long long)peers_hi << 32) | peers_lo;
-    const unsigned below = (unsigned)__popcll(peers & lanes_below);
+    const unsigned below = (unsigned)lane_rank_popc(peers);
     unsigned prev = 0;
     if (valid) {
       prev = sh.cnt[wave][d];
@@ -434,7 +420,8 @@ __device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT, typename S
 #pragma unroll
     for (int w = 0; w < RS_WAVES; ++w) total += sh.cnt[w][d];
     int block_total;
-    const unsigned local = (unsigned)block_exclusive_scan((int)total, sh.scan, &block_total);
+    const unsigned local = (unsigned)block_exclusive_sum<SCAN_WAVES>((int)total, sh.scan, &block_total);
+    __syncthreads();
     unsigned run = local;
 #pragma unroll
     for (int w = 0; w < RS_WAVES; ++w) {
@@ -445,7 +432,8 @@ __device__ __forceinline__ void downsweep_block(DownsweepShared<KeyT, typename S
     // global start of the digit = items of all smaller digits (256-entry scan, done by every block for itself)
     // + items of this digit in earlier blocks (radix_row_scan_kernel)
     int all_items;
-    const unsigned digit_base = (unsigned)block_exclusive_scan(digit_totals[d], sh.scan, &all_items);
+    const unsigned digit_base = (unsigned)block_exclusive_sum<SCAN_WAVES>(digit_totals[d], sh.scan, &all_items);
+    __syncthreads();
     sh.digit_shift[d] = digit_base + (unsigned)hist_scanned[(int64_t)d * num_blocks + blockIdx.x] - local;
   }
   __syncthreads();

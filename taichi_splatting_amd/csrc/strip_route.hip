@@ -84,11 +84,7 @@ route_offsets_kernel(int32_t* __restrict__ block_counts, int nblocks, int64_t* _
   for (int base = 0; base < nblocks; base += 1024) {
     const int i = base + threadIdx.x;
     const int x = i < nblocks ? c[i] : 0;
-    int incl = x;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += y;
-    }
+    const int incl = wave_inclusive_sum(x);
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     int wave_base = 0;

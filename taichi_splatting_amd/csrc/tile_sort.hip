@@ -36,53 +36,6 @@ struct TsShared {
 constexpr uint64_t TS_DECLINED = ~0ull;
 constexpr int TS_REPORT_ABOVE = 16384;      // runs longer than this are reported through ms_frame_inputs.longest_run_host
 
-__device__ __forceinline__ uint32_t ts_wave_min(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o); v = w < v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ uint32_t ts_wave_max(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o); v = w > v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ uint32_t ts_wave_or(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
-__device__ __forceinline__ uint32_t ts_wave_and(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v &= (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
-__device__ __forceinline__ uint32_t ts_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
-// inclusive prefix sum over the wave
-__device__ __forceinline__ uint32_t ts_wave_scan(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t w = (uint32_t)__shfl_up((int)v, o); if (lane >= o) v += w; }
-  return v;
-}
-
-// exclusive prefix sum of one value per thread over the workgroup; *total = the sum (uses red[0 .. TS_WAVES))
-__device__ __forceinline__ uint32_t ts_block_exclusive(uint32_t v, uint32_t* red, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t inc = ts_wave_scan(v);
-  __syncthreads();
-  if (lane == 63) red[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < TS_WAVES; ++w) { const uint32_t c = red[w]; if (w < wave) before += c; all += c; }
-  *total = all;
-  return before + inc - v;
-}
-
 // ---- bounded path: LSD radix sort of one run by the whole workgroup, on global memory ------------------------------
 // srt[b .. b + n): depth key << 32 | point index; o2p[b .. b + n): output only; alt: scratch of the same extent.
 // wcnt: TS_WAVES * 256 words of LDS (per-wave digit counters, then write positions)
@@ -95,8 +48,8 @@ __device__ void tile_radix_sort_global(uint64_t* srt, int32_t* o2p, uint64_t* al
     kor |= k;
     kand &= k;
   }
-  kor = ts_wave_or(kor);
-  kand = ts_wave_and(kand);
+  kor = wave_all(kor, [](uint32_t a, uint32_t b) { return a | b; });
+  kand = wave_all(kand, [](uint32_t a, uint32_t b) { return a & b; });
   __syncthreads();
   if (lane == 0) { sh.red[wave] = kor; sh.red[TS_WAVES + wave] = kand; }
   __syncthreads();
@@ -116,7 +69,9 @@ __device__ void tile_radix_sort_global(uint64_t* srt, int32_t* o2p, uint64_t* al
     for (int i = t; i < n; i += TS_THREADS) atomicAdd(&sh.hist[(uint32_t)(src[b + i] >> shift) & 0xffu], 1u);
     __syncthreads();
     uint32_t total;
-    const uint32_t base = ts_block_exclusive(sh.hist[t], sh.red, &total);
+    const uint32_t digits = sh.hist[t];
+    __syncthreads();                                             // sh.red: the reads of the vary test and of the pass before
+    const uint32_t base = block_exclusive_sum<TS_WAVES>(digits, sh.red, &total);
     __syncthreads();
     sh.hist[t] = base;                                           // running write position of digit t
     __syncthreads();
@@ -141,13 +96,13 @@ __device__ void tile_radix_sort_global(uint64_t* srt, int32_t* o2p, uint64_t* al
           const uint64_t bal = __ballot(one);
           peers &= one ? bal : ~bal;
         }
-        const uint64_t below = peers & ((1ull << lane) - 1ull);
+        const uint32_t below = (uint32_t)lane_rank_popc(peers);
         uint32_t prev = 0u;
         if (valid) prev = wcnt[wave * 256 + d];
         __builtin_amdgcn_wave_barrier();
-        if (valid && below == 0ull) wcnt[wave * 256 + d] = prev + (uint32_t)__popcll(peers);
+        if (valid && below == 0u) wcnt[wave * 256 + d] = prev + (uint32_t)__popcll(peers);
         __builtin_amdgcn_wave_barrier();
-        rank[g] = prev + (uint32_t)__popcll(below);
+        rank[g] = prev + below;
       }
       __syncthreads();
       {
@@ -201,8 +156,8 @@ __device__ __forceinline__ bool tile_bucket_sort(uint64_t* __restrict__ srt, int
       kmax = key[r] > kmax ? key[r] : kmax;
     }
   }
-  kmin = ts_wave_min(kmin);
-  kmax = ts_wave_max(kmax);
+  kmin = wave_all(kmin, [](uint32_t a, uint32_t b) { return b < a ? b : a; });
+  kmax = wave_all(kmax, [](uint32_t a, uint32_t b) { return b > a ? b : a; });
   if (lane == 0) { sh.red[wave] = kmin; sh.red[TS_WAVES + wave] = kmax; }
   __syncthreads();
 #pragma unroll
@@ -246,8 +201,8 @@ __device__ __forceinline__ bool tile_bucket_sort(uint64_t* __restrict__ srt, int
   uint32_t mine = 0u, squares = 0u;
   for (uint32_t j = j0; j < j1; ++j) { const uint32_t c = cnt[j]; mine += c; squares += c * c; }
   // exclusive scan of the per-thread sums and the total of the squares, through one pair of barriers
-  const uint32_t inc = ts_wave_scan(mine);
-  squares = ts_wave_sum(squares);
+  const uint32_t inc = wave_inclusive_sum(mine);
+  squares = wave_all(squares, [](uint32_t a, uint32_t b) { return a + b; });
   if (lane == 63) { sh.red[wave] = inc; sh.red[TS_WAVES + wave] = squares; }
   __syncthreads();
   uint32_t run = inc - mine, cost = 0u;

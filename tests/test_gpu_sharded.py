@@ -218,6 +218,57 @@ def test_return_rows_and_slot_table_match_return_grads(world, capacity_frac):
   assert torch.allclose(gathered, want, rtol=1e-5, atol=1e-5)
 
 
+_ROUNDS_SIZE, _ROUNDS_MAX_N = (256, 512), 2 * 1024 * 256
+_rounds_splats = []       # [projected splats, depths] of the largest case, made once; smaller cases take a prefix
+
+
+@pytest.mark.parametrize('n', [1024 * 256 + 1, _ROUNDS_MAX_N])
+@pytest.mark.parametrize('world,bounds', [(1, None), (3, None), (3, [0, 0, 16, 32])])
+def test_route_offsets_carry_the_total_across_rounds(world, bounds, n):
+  """route_offsets_kernel scans 1024 blocks per round and carries the total into the next one: 1025 blocks (the smallest
+  count with a second round) and 2048 (a full last round), against numpy on the returned route words.  The repeated
+  bound leaves strip 0 without a tile row: a destination that receives nothing.  Integers: exact."""
+  import ctypes
+  import numpy as np
+  from taichi_splatting_amd import RasterConfig, _lib
+  from taichi_splatting_amd import distributed as D
+  from taichi_splatting_amd.misc.renderer2d import project_gaussians2d
+  from taichi_splatting_amd.testing import random_2d_gaussians
+  lib = _lib.load()
+  if not _rounds_splats:
+    torch.manual_seed(0)
+    g = random_2d_gaussians(_ROUNDS_MAX_N, _ROUNDS_SIZE, scale_factor=3.0, alpha_range=(0.05, 0.9)).to(DEV)
+    _rounds_splats.extend([project_gaussians2d(g).contiguous(), g.depths.reshape(-1).contiguous()])
+  p, depth = _rounds_splats[0][:n], _rounds_splats[1][:n]
+  cfg = RasterConfig()
+  tiles_high = (_ROUNDS_SIZE[1] + 15) // 16
+  if bounds is None:
+    bounds = D.strip_bounds(tiles_high, world)
+  nb = lib.ms_strip_route_blocks(n)
+  assert nb == (n + 255) // 256 and nb > 1024
+  route = torch.empty((n,), dtype=torch.int32, device=DEV)
+  block_offsets = torch.full((world * nb,), -1, dtype=torch.int32, device=DEV)
+  send_counts = torch.full((world,), -1, dtype=torch.int64, device=DEV)
+  bounds_c = (ctypes.c_int32 * (world + 1))(*bounds)
+  _lib.check(lib.ms_strip_route_count(p.data_ptr(), depth.data_ptr(), n, _ROUNDS_SIZE[1], cfg.tile_size, cfg.alpha_threshold,
+                                      ctypes.cast(bounds_c, ctypes.c_void_p), world, route.data_ptr(),
+                                      block_offsets.data_ptr(), send_counts.data_ptr(), _lib.current_stream(p.device)), 'count')
+  word = route.cpu().numpy()
+  first, copies = (word & 0xffff).astype(np.int64), (word >> 16).astype(np.int64)
+  got_offsets, got_counts = block_offsets.cpu().numpy().reshape(world, nb), send_counts.cpu().numpy()
+  for d in range(world):
+    routed = np.zeros((nb * 256,), dtype=np.int64)
+    routed[:n] = (first <= d) & (d < first + copies)
+    per_block = routed.reshape(nb, 256).sum(axis=1)
+    assert np.array_equal(got_offsets[d], np.cumsum(per_block) - per_block), d
+    assert got_counts[d] == per_block.sum(), d
+  assert got_counts.sum() > n // 2
+  if bounds[0] == bounds[1]:
+    assert got_counts[0] == 0 and (got_counts[1:] > 0).all()
+  else:
+    assert (got_counts > 0).all()
+
+
 @pytest.mark.parametrize('world,dtype_name,balance', [(2, 'float64', False), (3, 'float64', True), (4, 'float32', False),
                                                       (3, 'float32', True), (8, 'float32', False)])
 def test_sharded_step_matches_full_frame(world, dtype_name, balance):
