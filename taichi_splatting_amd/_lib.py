@@ -311,6 +311,11 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
   return t.data_ptr()
 
 
+def row_bytes(t: torch.Tensor, n: int) -> int:
+  """Bytes per row of a contiguous tensor of ``n`` rows (the ``row_bytes`` of a row descriptor)."""
+  return (t.numel() // n) * t.element_size()
+
+
 def require_gpu(*tensors: torch.Tensor):
   for t in tensors:
     if t is not None and not t.is_cuda:

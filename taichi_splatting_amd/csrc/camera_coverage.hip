@@ -113,12 +113,9 @@ extern "C" int ms_camera_coverage(const void* position, const void* log_scaling,
   MS_CHECK_ARG(n <= INT32_MAX, "n < 2^31 expected");
   MS_CHECK_ARG(num_cameras >= 1 && num_cameras <= MS_COVERAGE_MAX_CAMERAS, "1 <= num_cameras <= 65535 expected");
   MS_CHECK_ARG(dtype == MS_F32 || dtype == MS_F64, "dtype must be MS_F32 or MS_F64");
-  const void* typed[7] = {position, log_scaling, rotation, alpha_logit, cameras, out_max_rate, out_min_depth};
-  uintptr_t bits = 0;
-  for (const void* p : typed) bits |= reinterpret_cast<uintptr_t>(p);
-  MS_CHECK_ARG((bits & (dtype == MS_F64 ? 7 : 3)) == 0, "every pointer must be aligned to its element type");
-  MS_CHECK_ARG(((reinterpret_cast<uintptr_t>(out_count) | reinterpret_cast<uintptr_t>(out_mask)) & 3) == 0,
-               "out_count and out_mask must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(dtype == MS_F64 ? 8 : 4, {position, log_scaling, rotation, alpha_logit, cameras, out_max_rate, out_min_depth}),
+               "every pointer must be aligned to its element type");
+  MS_CHECK_ARG(aligned(4, {out_count, out_mask}), "out_count and out_mask must be aligned to 4 bytes");
   if (n == 0) return 0;
   MS_CHECK_ARG(position && log_scaling && rotation && alpha_logit, "null gaussian input");
   MS_CHECK_ARG(cameras != nullptr, "null cameras");

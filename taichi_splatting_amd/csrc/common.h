@@ -1,11 +1,14 @@
 // common.h — shared host/device helpers for the gfx950 kernels (wave64 only): error reporting, scratch blocks, splat
 // rows, the depth sort key.  The wave and block primitives (lane_id, DPP moves, butterflies, scans, ballot ranks,
-// one-atomic-per-block commits) live in wave.h, which this header includes.
+// one-atomic-per-block commits) live in wave.h, the row pieces and the walk of the row movers in rows.h; this header
+// includes both.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "../../include/mi355_splat.h"
 #include "splat_math.h"
@@ -44,6 +47,19 @@ void set_error(const char* fmt, ...);
 
 static inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+
+// every pointer is a multiple of `bytes` (a power of two); a null pointer counts as aligned
+static inline bool aligned(uintptr_t bytes, std::initializer_list<const void*> pointers) {
+  uintptr_t bits = 0;
+  for (const void* p : pointers) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & (bytes - 1)) == 0;
+}
+
+}  // namespace ms
+
+#include "rows.h"      // after set_error and aligned, which its host side uses
+
+namespace ms {
 
 // ---- scratch blocks: the (tmp, tmp_bytes) convention of include/mi355_splat.h ------------------------------------
 // Every entry point with a scratch block lays it out with ONE Carve and answers the two-call protocol with ONE

@@ -20,11 +20,7 @@
 
 namespace ms {
 
-constexpr int DENSIFY_ROWS = 256;          // destination rows per workgroup
-constexpr int DENSIFY_MAX_ARRAYS = 32;     // arrays per launch (a 3-D scene with Adam-like state has 17)
-constexpr int DENSIFY_UNROLL = 4;          // pieces in flight per lane
-constexpr int32_t CHILD_BIT = 1 << 30;     // LDS encoding of a table row: source row | CHILD_BIT, or -1 (write zeros)
-constexpr int64_t DENSIFY_MAX_ROW_BYTES = 1 << 20;
+constexpr int32_t CHILD_BIT = ROW_FLAG_BIT;     // LDS encoding of a table row: source row | CHILD_BIT, or -1 (write zeros)
 
 // keep = !(prune | split), split = split & !prune, as int32 for the scan: out[i] = keep, out[n + i] = split
 __global__ void __launch_bounds__(256)
@@ -81,16 +77,15 @@ struct MoveArgs {
   const int32_t* child_slot;
   int64_t n_src, n_out;
   int num_arrays;
-  MoveArray a[DENSIFY_MAX_ARRAYS];
+  MoveArray a[ROW_MAX_ARRAYS];
 };
 
-template <typename P> __device__ __forceinline__ P zero_piece();
-template <> __device__ __forceinline__ uint32_t zero_piece<uint32_t>() { return 0u; }
+// The move keeps uint32_t / uint4 as its pieces: with piece4 / piece16 of rows.h the compiler schedules
+// densify_move_kernel differently (one instruction more).
 template <> __device__ __forceinline__ uint4 zero_piece<uint4>() { return make_uint4(0u, 0u, 0u, 0u); }
 
 // The block's rows of one array: pieces p = 0 .. rows * row_pieces - 1 of the contiguous destination range, lane t takes
-// p = t, t + 256, ...; (row, piece in row) advance by (256 / row_pieces, 256 % row_pieces) with one carry: no division
-// inside the loop.
+// p = t, t + 256, ... and follows its (row, piece in row) with a PieceWalk (rows.h).
 template <typename P>
 __device__ __forceinline__ void move_array(const MoveArray& a, const int32_t* enc, int rows, int64_t first) {
   const uint32_t ppr = a.row_pieces;
@@ -98,34 +93,32 @@ __device__ __forceinline__ void move_array(const MoveArray& a, const int32_t* en
   const bool copy_children = (a.flags & 1u) != 0;
   const P* __restrict__ src = reinterpret_cast<const P*>(a.src);
   P* __restrict__ dst = reinterpret_cast<P*>(a.dst) + first * (int64_t)ppr;
-  const uint32_t step_r = 256u / ppr, step_k = 256u % ppr;
-  uint32_t r = threadIdx.x / ppr, k = threadIdx.x % ppr;
+  PieceWalk w(threadIdx.x, ppr);
 #pragma unroll 1
-  for (uint32_t p = threadIdx.x; p < total; p += 256u * DENSIFY_UNROLL) {
-    P v[DENSIFY_UNROLL];
+  for (uint32_t p = threadIdx.x; p < total; p += 256u * ROW_UNROLL) {
+    P v[ROW_UNROLL];
 #pragma unroll
-    for (int u = 0; u < DENSIFY_UNROLL; ++u) {
+    for (int u = 0; u < ROW_UNROLL; ++u) {
       v[u] = zero_piece<P>();
       if (p + 256u * u < total) {
-        const int32_t e = enc[r];
+        const int32_t e = enc[w.r];
         if (e >= 0 && (copy_children || !(e & CHILD_BIT)))
-          v[u] = src[(int64_t)(e & (CHILD_BIT - 1)) * (int64_t)ppr + k];
+          v[u] = src[(int64_t)(e & (CHILD_BIT - 1)) * (int64_t)ppr + w.k];
       }
-      r += step_r; k += step_k;
-      if (k >= ppr) { k -= ppr; ++r; }
+      w.advance();
     }
 #pragma unroll
-    for (int u = 0; u < DENSIFY_UNROLL; ++u)
+    for (int u = 0; u < ROW_UNROLL; ++u)
       if (p + 256u * u < total) dst[p + 256u * u] = v[u];
   }
 }
 
 __global__ void __launch_bounds__(256)
 densify_move_kernel(MoveArgs m) {
-  __shared__ int32_t enc[DENSIFY_ROWS];
-  const int64_t first = (int64_t)blockIdx.x * DENSIFY_ROWS;
+  __shared__ int32_t enc[ROW_BLOCK];
+  const int64_t first = (int64_t)blockIdx.x * ROW_BLOCK;
   const int64_t left = m.n_out - first;
-  const int rows = left < DENSIFY_ROWS ? (int)left : DENSIFY_ROWS;
+  const int rows = left < ROW_BLOCK ? (int)left : ROW_BLOCK;
   {
     int32_t e = -1;
     if ((int)threadIdx.x < rows) {
@@ -201,8 +194,6 @@ densify_split3d_kernel(float* __restrict__ position, float* __restrict__ log_sca
 
 using namespace ms;
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int check_plan_sizes(int64_t n, int children, const char* who) {
   if (n < 0) { set_error("%s: n >= 0 expected", who); return MS_ERR_BAD_ARG; }
   if (children < 1) { set_error("%s: children >= 1 expected (got %d)", who, children); return MS_ERR_BAD_ARG; }
@@ -253,19 +244,11 @@ extern "C" int ms_densify_move(const ms_densify_array* arrays, int num_arrays, c
   // every descriptor is checked before the first launch: an error return leaves every array as it was
   for (int i = 0; i < num_arrays; ++i) {
     const ms_densify_array& a = arrays[i];
-    if (a.struct_size != sizeof(ms_densify_array)) {
-      set_error("ms_densify_move: ms_densify_array of another ABI (struct_size %u, this library: %u)", a.struct_size,
-                (unsigned)sizeof(ms_densify_array));
-      return MS_ERR_ABI;
-    }
-    if (a.row_bytes <= 0 || a.row_bytes % 4 != 0 || a.row_bytes > DENSIFY_MAX_ROW_BYTES) {
-      set_error("ms_densify_move: array %d: row_bytes must be a positive multiple of 4, at most %lld (got %lld)", i,
-                (long long)DENSIFY_MAX_ROW_BYTES, (long long)a.row_bytes);
-      return MS_ERR_BAD_ARG;
-    }
+    const int rc = check_row_array(__func__, i, a.struct_size, sizeof(ms_densify_array), a.row_bytes);
+    if (rc) return rc;
     if (a.child_fill != 0 && a.child_fill != 1) { set_error("ms_densify_move: array %d: child_fill must be 0 (zero) or 1 (copy the parent)", i); return MS_ERR_BAD_ARG; }
     if (!a.src || !a.dst) { set_error("ms_densify_move: array %d: null pointer", i); return MS_ERR_BAD_ARG; }
-    if ((reinterpret_cast<uintptr_t>(a.src) | reinterpret_cast<uintptr_t>(a.dst)) & 3) {
+    if (!aligned(4, {a.src, a.dst})) {
       set_error("ms_densify_move: array %d: bases must be 4-byte aligned", i);
       return MS_ERR_BAD_ARG;
     }
@@ -274,15 +257,15 @@ extern "C" int ms_densify_move(const ms_densify_array* arrays, int num_arrays, c
   MS_CHECK_ARG(src_row && child_slot, "null source table");
   MoveArgs m{};
   m.src_row = src_row; m.child_slot = child_slot; m.n_src = n_src; m.n_out = n_out;
-  const dim3 grid((unsigned)div_up(n_out, DENSIFY_ROWS));
+  const dim3 grid((unsigned)div_up(n_out, ROW_BLOCK));
   for (int i = 0; i < num_arrays; ++i) {
     const ms_densify_array& a = arrays[i];
-    const bool vec = a.row_bytes % 16 == 0 && aligned16(a.src) && aligned16(a.dst);
+    const RowPieces pieces(a.row_bytes, {a.src, a.dst});
     MoveArray& out = m.a[m.num_arrays++];
     out.src = (const char*)a.src; out.dst = (char*)a.dst;
-    out.row_pieces = (uint32_t)(a.row_bytes / (vec ? 16 : 4));
-    out.flags = (a.child_fill ? 1u : 0u) | (vec ? 2u : 0u);
-    if (m.num_arrays == DENSIFY_MAX_ARRAYS || i == num_arrays - 1) {
+    out.row_pieces = pieces.row_pieces;
+    out.flags = (a.child_fill ? 1u : 0u) | (pieces.vec ? 2u : 0u);
+    if (m.num_arrays == ROW_MAX_ARRAYS || i == num_arrays - 1) {
       densify_move_kernel<<<grid, dim3(256), 0, (hipStream_t)stream>>>(m);
       MS_CHECK_LAUNCH();
       m.num_arrays = 0;

@@ -489,7 +489,7 @@ extern "C" int ms_map_tiles_direct(const float* points7, const void* depth, int 
   const size_t hist = c.take(sort_hist_size(k_capacity));
   MS_CHECK_TMP(scratch, scratch_bytes, c.off);
   MS_CHECK_ARG(out_tile_ranges && out_counters, "null pointer");
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "scratch must be 16-byte aligned");
+  MS_CHECK_ARG(aligned(16, {scratch}), "scratch must be 16-byte aligned");
 
   hipStream_t s = (hipStream_t)stream;
   MS_CHECK_HIP(hipMemsetAsync(out_counters, 0, 8 * sizeof(int32_t), s));

@@ -473,10 +473,7 @@ static int launch_typed(const GaussianBwdArgs& g, hipStream_t s) {
     if (mom) {
       // 16-byte DMA pieces want 16-byte aligned sources (a caller's tensor may be a view at any multiple of 4), the
       // 4- and 12-byte ones only the alignment of a float
-      a.stage_inputs = ((reinterpret_cast<uintptr_t>(g.rotation) | reinterpret_cast<uintptr_t>(g.moments)) & 15) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(g.position) | reinterpret_cast<uintptr_t>(g.log_scaling) |
-                         reinterpret_cast<uintptr_t>(g.alpha_logit) | reinterpret_cast<uintptr_t>(g.depth) |
-                         reinterpret_cast<uintptr_t>(g.colours)) & 3) == 0;
+      a.stage_inputs = aligned(16, {g.rotation, g.moments}) && aligned(4, {g.position, g.log_scaling, g.alpha_logit, g.depth, g.colours});
     }
   }
   if (g.grad_camera && blocks > 2048) blocks = 2048;      // bounded atomic count for the 16 camera sums

@@ -48,9 +48,7 @@
 //   divided by its double length, rounded once; a zero (or non-finite) length gives (0, 0, 0).  A face with an index
 //   outside 0 .. V - 1 contributes nothing.  A vertex of very high degree is legal and merely slow (one lane walks it).
 #pragma clang fp contract(off)
-#include "common.h"
-
-#include <initializer_list>
+#include "mesh_internal.h"
 
 namespace ms {
 
@@ -87,10 +85,6 @@ __device__ __forceinline__ bool mesh_unite(int32_t* __restrict__ parent, int32_t
     rb = mesh_find(parent, lo, limit);
   }
   return ra == rb;
-}
-
-__device__ __forceinline__ bool mesh_in_range(int32_t a, int32_t b, int32_t c, int32_t num_vertices) {
-  return (uint32_t)a < (uint32_t)num_vertices && (uint32_t)b < (uint32_t)num_vertices && (uint32_t)c < (uint32_t)num_vertices;
 }
 
 __global__ void __launch_bounds__(256)
@@ -313,15 +307,6 @@ mesh_normals_kernel(const float* __restrict__ vertices, const int32_t* __restric
   }
 }
 
-static bool mesh_sizes_ok(int64_t num_vertices, int64_t num_faces) {
-  return num_vertices >= 0 && num_faces >= 0 && num_vertices <= MS_MESH_MAX_VERTICES && num_faces <= MS_MESH_MAX_CORNERS / 3;
-}
-static bool mesh_aligned4(std::initializer_list<const void*> pointers) {
-  uintptr_t bits = 0;
-  for (const void* p : pointers) bits |= reinterpret_cast<uintptr_t>(p);
-  return (bits & 3) == 0;
-}
-static dim3 mesh_grid(int64_t n) { return dim3((unsigned)div_up(n > 0 ? n : 1, 256)); }
 static int mesh_key_bits(int64_t largest) {
   int bits = 1;
   while (bits < 32 && ((int64_t)1 << bits) <= largest) ++bits;
@@ -385,11 +370,11 @@ extern "C" int ms_mesh_components(const int32_t* faces, int64_t num_vertices, in
   MS_CHECK_ARG(mesh_sizes_ok(num_vertices, num_faces), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected");
   const MeshComponentsTmp lay = mesh_components_tmp(num_vertices);
   MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
+  MS_CHECK_ARG(aligned(256, {tmp}), "tmp must be aligned to 256 bytes");
   MS_CHECK_ARG(head != nullptr, "head is null");
   MS_CHECK_ARG((faces && face_label) || num_faces == 0, "null faces or face_label");
   MS_CHECK_ARG(vertex_label || num_vertices == 0, "null vertex_label");
-  MS_CHECK_ARG(mesh_aligned4({faces, vertex_label, face_label, head}), "every pointer must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {faces, vertex_label, face_label, head}), "every pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
   int32_t* status = at<int32_t>(tmp, lay.status);
   int32_t* parent = at<int32_t>(tmp, lay.parent);
@@ -417,7 +402,7 @@ extern "C" int ms_mesh_component_counts(const int32_t* vertex_label, int64_t num
   MS_CHECK_ARG(num_components >= 0 && num_components <= num_vertices, "0 <= K <= V expected");
   if (num_components == 0) return 0;
   MS_CHECK_ARG(vertex_label && vertex_count && face_count && (face_label || num_faces == 0), "null pointer");
-  MS_CHECK_ARG(mesh_aligned4({vertex_label, face_label, vertex_count, face_count}), "every pointer must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {vertex_label, face_label, vertex_count, face_count}), "every pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
   MS_CHECK_HIP(hipMemsetAsync(vertex_count, 0, (size_t)num_components * 4, s));
   MS_CHECK_HIP(hipMemsetAsync(face_count, 0, (size_t)num_components * 4, s));
@@ -438,10 +423,10 @@ extern "C" int ms_mesh_component_filter(const int32_t* face_count, int64_t num_c
   MS_CHECK_ARG(keep_largest >= 0, "keep_largest >= 1 (or 0: every component) expected");
   const MeshSortTmp lay = mesh_filter_tmp(num_components);
   MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
+  MS_CHECK_ARG(aligned(256, {tmp}), "tmp must be aligned to 256 bytes");
   if (num_faces == 0) return 0;
   MS_CHECK_ARG(face_label && face_mask && (face_count || num_components == 0), "null pointer");
-  MS_CHECK_ARG(mesh_aligned4({face_count, face_label}), "face_count and face_label must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {face_count, face_label}), "face_count and face_label must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
   uint32_t* keys = at<uint32_t>(tmp, lay.keys);
   int32_t* values = at<int32_t>(tmp, lay.values);
@@ -473,10 +458,10 @@ extern "C" int ms_mesh_select_plan(const int32_t* faces, const uint8_t* face_mas
   MS_CHECK_ARG(mesh_sizes_ok(num_vertices, num_faces), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected");
   const MeshSelectTmp lay = mesh_select_tmp(num_vertices, num_faces);
   MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
+  MS_CHECK_ARG(aligned(256, {tmp}), "tmp must be aligned to 256 bytes");
   MS_CHECK_ARG(vertex_scan && face_scan && head, "null vertex_scan, face_scan or head");
   MS_CHECK_ARG((faces && face_mask) || num_faces == 0, "null faces or face_mask");
-  MS_CHECK_ARG(mesh_aligned4({faces, vertex_scan, face_scan, head}), "every int32 pointer must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {faces, vertex_scan, face_scan, head}), "every int32 pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
   int32_t* status = at<int32_t>(tmp, lay.status);
   MS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
@@ -510,7 +495,7 @@ extern "C" int ms_mesh_select_gather(const float* vertices, const float* colours
   MS_CHECK_ARG((faces && face_mask && out_faces) || num_faces == 0, "null faces, face_mask or out_faces");
   MS_CHECK_ARG((colours == nullptr) == (out_colours == nullptr) && (normals == nullptr) == (out_normals == nullptr),
                "colours and normals are given together with their outputs");
-  MS_CHECK_ARG(mesh_aligned4({vertices, colours, normals, faces, vertex_scan, face_scan, out_vertices, out_colours, out_normals,
+  MS_CHECK_ARG(aligned(4, {vertices, colours, normals, faces, vertex_scan, face_scan, out_vertices, out_colours, out_normals,
                               out_faces}), "every pointer but face_mask must be aligned to 4 bytes");
   mesh_gather_kernel<<<mesh_grid(num_vertices > num_faces ? num_vertices : num_faces), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint32_t*)vertices, (const uint32_t*)colours, (const uint32_t*)normals, faces, face_mask, (int32_t)num_vertices,
@@ -524,11 +509,11 @@ extern "C" int ms_mesh_vertex_normals(const float* vertices, const int32_t* face
   MS_CHECK_ARG(mesh_sizes_ok(num_vertices, num_faces), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected");
   const MeshSortTmp lay = mesh_normals_tmp(num_vertices, num_faces);
   MS_CHECK_TMP(tmp, tmp_bytes, lay.total);
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "tmp must be aligned to 256 bytes");
+  MS_CHECK_ARG(aligned(256, {tmp}), "tmp must be aligned to 256 bytes");
   if (num_vertices == 0) return 0;
   MS_CHECK_ARG(vertices && (faces || num_faces == 0), "null vertices or faces");
   MS_CHECK_ARG(out_sums || out_normals, "out_sums and out_normals are both null");
-  MS_CHECK_ARG(mesh_aligned4({vertices, faces, out_sums, out_normals}), "every pointer must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {vertices, faces, out_sums, out_normals}), "every pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
   uint32_t* keys = at<uint32_t>(tmp, lay.keys);
   int32_t* values = at<int32_t>(tmp, lay.values);

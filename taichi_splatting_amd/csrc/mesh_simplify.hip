@@ -36,9 +36,7 @@
 //     scatters the flag by face index.
 //   simplify_map_kernel       vertex_map[v] = the output vertex of v's cluster after ms_mesh_select_plan's compaction, or -1.
 #pragma clang fp contract(off)
-#include "common.h"
-
-#include <initializer_list>
+#include "mesh_internal.h"
 
 namespace ms {
 
@@ -62,10 +60,6 @@ __device__ __forceinline__ uint64_t simplify_cell_key(float x, float y, float z,
               qz = simplify_cell_axis(z, oz, cell_size);
   if (!(simplify_cell_valid(qx) && simplify_cell_valid(qy) && simplify_cell_valid(qz))) return SIMPLIFY_NO_CELL;
   return ((uint64_t)(uint32_t)qz << (2 * SIMPLIFY_CELL_BITS)) | ((uint64_t)(uint32_t)qy << SIMPLIFY_CELL_BITS) | (uint64_t)(uint32_t)qx;
-}
-
-__device__ __forceinline__ bool simplify_in_range(int32_t a, int32_t b, int32_t c, int32_t n) {
-  return (uint32_t)a < (uint32_t)n && (uint32_t)b < (uint32_t)n && (uint32_t)c < (uint32_t)n;
 }
 
 __device__ __forceinline__ bool simplify_finite(double v) { return v - v == 0.0; }
@@ -112,7 +106,7 @@ simplify_mark_kernel(const int32_t* __restrict__ faces, int32_t num_vertices, in
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= num_faces) return;
   const int32_t a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-  if (!simplify_in_range(a, b, c, num_vertices)) {
+  if (!mesh_in_range(a, b, c, num_vertices)) {
     atomicOr(status, MS_MESH_BAD_INDEX);
     return;
   }
@@ -249,7 +243,7 @@ simplify_place_kernel(const float* __restrict__ vertices, const float* __restric
       if ((uint32_t)corner >= (uint64_t)num_corners) continue;
       const int64_t f = corner / 3;
       const int32_t a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-      if (!simplify_in_range(a, b, c, num_vertices)) continue;
+      if (!mesh_in_range(a, b, c, num_vertices)) continue;
       const double px = vertices[(int64_t)a * 3 + 0], py = vertices[(int64_t)a * 3 + 1], pz = vertices[(int64_t)a * 3 + 2];
       const double ux = (double)vertices[(int64_t)b * 3 + 0] - px, uy = (double)vertices[(int64_t)b * 3 + 1] - py,
                    uz = (double)vertices[(int64_t)b * 3 + 2] - pz;
@@ -335,12 +329,12 @@ simplify_faces_kernel(const int32_t* __restrict__ faces, int32_t num_vertices, i
   if (f >= num_faces) return;
   const int32_t a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
   int32_t p = -1, q = -1, r = -1;
-  if (simplify_in_range(a, b, c, num_vertices)) {
+  if (mesh_in_range(a, b, c, num_vertices)) {
     p = vertex_cluster[a];
     q = vertex_cluster[b];
     r = vertex_cluster[c];
   }
-  const bool kept = simplify_in_range(p, q, r, num_clusters) && p != q && q != r && r != p;
+  const bool kept = mesh_in_range(p, q, r, num_clusters) && p != q && q != r && r != p;
   if (!kept) {
     p = q = r = 0;                                                    // not a triangle: never kept, never read as one
   } else if (q < p && q < r) {                                        // rotate the smallest first: the orientation stays
@@ -399,27 +393,18 @@ simplify_map_kernel(const int32_t* __restrict__ vertex_cluster, int32_t num_vert
   vertex_map[v] = to;
 }
 
-static bool simplify_sizes_ok(int64_t num_vertices, int64_t num_faces) {
-  return num_vertices >= 0 && num_faces >= 0 && num_vertices <= MS_MESH_MAX_VERTICES && num_faces <= MS_MESH_MAX_CORNERS / 3;
-}
-static bool simplify_aligned(std::initializer_list<const void*> pointers, uintptr_t mask) {
-  uintptr_t bits = 0;
-  for (const void* p : pointers) bits |= reinterpret_cast<uintptr_t>(p);
-  return (bits & mask) == 0;
-}
-static dim3 simplify_grid(int64_t n) { return dim3((unsigned)div_up(n > 0 ? n : 1, 256)); }
 
 }  // namespace ms
 
 using namespace ms;
 
 #define SIMPLIFY_CHECK_SIZES(v, f) \
-  MS_CHECK_ARG(simplify_sizes_ok(v, f), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected")
+  MS_CHECK_ARG(mesh_sizes_ok(v, f), "0 <= V <= 2^31 - 1 and 0 <= 3 T <= 2^31 - 1 expected")
 
 extern "C" int ms_mesh_simplify_origin(const float* vertices, int64_t num_vertices, float* origin, void* stream) {
   SIMPLIFY_CHECK_SIZES(num_vertices, 0);
   MS_CHECK_ARG(origin && (vertices || num_vertices == 0), "null origin or vertices");
-  MS_CHECK_ARG(simplify_aligned({vertices, origin}, 3), "every pointer must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {vertices, origin}), "every pointer must be aligned to 4 bytes");
   hipStream_t s = (hipStream_t)stream;
   if (num_vertices == 0) {
     MS_CHECK_HIP(hipMemsetAsync(origin, 0, 3 * sizeof(float), s));
@@ -440,20 +425,20 @@ extern "C" int ms_mesh_simplify_keys(const float* vertices, const int32_t* faces
   MS_CHECK_ARG(status && head && origin, "null status, head or origin");
   MS_CHECK_ARG((vertices && referenced && keys && values) || num_vertices == 0, "null vertices, referenced, keys or values");
   MS_CHECK_ARG(faces || num_faces == 0, "null faces");
-  MS_CHECK_ARG(simplify_aligned({vertices, faces, origin, referenced, values, status, head}, 3) && simplify_aligned({keys}, 7),
+  MS_CHECK_ARG(aligned(4, {vertices, faces, origin, referenced, values, status, head}) && aligned(8, {keys}),
                "every pointer must be aligned to 4 bytes, keys to 8");
   hipStream_t s = (hipStream_t)stream;
   MS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
   MS_CHECK_HIP(hipMemsetAsync(head, 0xff, 2 * sizeof(int32_t), s));        // poisoned until ms_mesh_simplify_clusters ran
   if (num_vertices == 0) {
-    if (num_faces > 0) simplify_mark_kernel<<<simplify_grid(num_faces), dim3(256), 0, s>>>(faces, 0, num_faces, nullptr, status);
+    if (num_faces > 0) simplify_mark_kernel<<<mesh_grid(num_faces), dim3(256), 0, s>>>(faces, 0, num_faces, nullptr, status);
     MS_CHECK_LAUNCH();
     return 0;
   }
   MS_CHECK_HIP(hipMemsetAsync(referenced, 0, (size_t)num_vertices * 4, s));
   if (num_faces > 0)
-    simplify_mark_kernel<<<simplify_grid(num_faces), dim3(256), 0, s>>>(faces, (int32_t)num_vertices, num_faces, referenced, status);
-  simplify_keys_kernel<<<simplify_grid(num_vertices), dim3(256), 0, s>>>(vertices, (int32_t)num_vertices, referenced, origin,
+    simplify_mark_kernel<<<mesh_grid(num_faces), dim3(256), 0, s>>>(faces, (int32_t)num_vertices, num_faces, referenced, status);
+  simplify_keys_kernel<<<mesh_grid(num_vertices), dim3(256), 0, s>>>(vertices, (int32_t)num_vertices, referenced, origin,
                                                                        cell_size, keys, values, status);
   MS_CHECK_LAUNCH();
   return 0;
@@ -463,9 +448,9 @@ extern "C" int ms_mesh_simplify_heads(const uint64_t* sorted_keys, int64_t num_v
   SIMPLIFY_CHECK_SIZES(num_vertices, 0);
   MS_CHECK_ARG(head_flag != nullptr, "null head_flag");
   MS_CHECK_ARG(sorted_keys || num_vertices == 0, "null sorted_keys");
-  MS_CHECK_ARG(simplify_aligned({head_flag}, 3) && simplify_aligned({sorted_keys}, 7), "head_flag aligned to 4 bytes, sorted_keys to 8");
+  MS_CHECK_ARG(aligned(4, {head_flag}) && aligned(8, {sorted_keys}), "head_flag aligned to 4 bytes, sorted_keys to 8");
   if (num_vertices == 0) return 0;
-  simplify_heads_kernel<<<simplify_grid(num_vertices), dim3(256), 0, (hipStream_t)stream>>>(sorted_keys, (int32_t)num_vertices, head_flag);
+  simplify_heads_kernel<<<mesh_grid(num_vertices), dim3(256), 0, (hipStream_t)stream>>>(sorted_keys, (int32_t)num_vertices, head_flag);
   MS_CHECK_LAUNCH();
   return 0;
 }
@@ -476,9 +461,9 @@ extern "C" int ms_mesh_simplify_clusters(const uint64_t* sorted_keys, const int3
   SIMPLIFY_CHECK_SIZES(num_vertices, 0);
   MS_CHECK_ARG(head_scan && member_begin && status && head, "null head_scan, member_begin, status or head");
   MS_CHECK_ARG((sorted_keys && sorted_vertices && vertex_cluster) || num_vertices == 0, "null sorted_keys, sorted_vertices or vertex_cluster");
-  MS_CHECK_ARG(simplify_aligned({sorted_vertices, head_scan, vertex_cluster, member_begin, status, head}, 3) &&
-               simplify_aligned({sorted_keys}, 7), "every pointer must be aligned to 4 bytes, sorted_keys to 8");
-  simplify_clusters_kernel<<<simplify_grid(num_vertices + 1), dim3(256), 0, (hipStream_t)stream>>>(
+  MS_CHECK_ARG(aligned(4, {sorted_vertices, head_scan, vertex_cluster, member_begin, status, head}) &&
+               aligned(8, {sorted_keys}), "every pointer must be aligned to 4 bytes, sorted_keys to 8");
+  simplify_clusters_kernel<<<mesh_grid(num_vertices + 1), dim3(256), 0, (hipStream_t)stream>>>(
       sorted_keys, sorted_vertices, head_scan, (int32_t)num_vertices, vertex_cluster, member_begin, status, head);
   MS_CHECK_LAUNCH();
   return 0;
@@ -491,8 +476,8 @@ extern "C" int ms_mesh_simplify_corner_keys(const int32_t* faces, int64_t num_ve
   MS_CHECK_ARG(num_clusters >= 0 && num_clusters <= num_vertices, "0 <= K <= V expected");
   if (num_faces == 0) return 0;
   MS_CHECK_ARG(faces && keys && values && (vertex_cluster || num_vertices == 0), "null pointer");
-  MS_CHECK_ARG(simplify_aligned({faces, vertex_cluster, keys, values}, 3), "every pointer must be aligned to 4 bytes");
-  simplify_corner_keys_kernel<<<simplify_grid(3 * num_faces), dim3(256), 0, (hipStream_t)stream>>>(
+  MS_CHECK_ARG(aligned(4, {faces, vertex_cluster, keys, values}), "every pointer must be aligned to 4 bytes");
+  simplify_corner_keys_kernel<<<mesh_grid(3 * num_faces), dim3(256), 0, (hipStream_t)stream>>>(
       faces, (int32_t)num_vertices, 3 * num_faces, vertex_cluster, (int32_t)num_clusters, keys, values);
   MS_CHECK_LAUNCH();
   return 0;
@@ -515,8 +500,8 @@ extern "C" int ms_mesh_simplify_place(const float* vertices, const float* colour
   MS_CHECK_ARG(vertices && origin && sorted_keys && sorted_vertices && member_begin && out_vertices, "null pointer");
   MS_CHECK_ARG(!quadric || (faces && corner_ranges && sorted_corners), "the quadric placement needs faces, corner_ranges and sorted_corners");
   MS_CHECK_ARG((colours == nullptr) == (out_colours == nullptr), "colours is given together with out_colours");
-  MS_CHECK_ARG(simplify_aligned({vertices, colours, faces, origin, sorted_vertices, member_begin, corner_ranges, sorted_corners,
-                                 out_vertices, out_colours}, 3) && simplify_aligned({sorted_keys}, 7),
+  MS_CHECK_ARG(aligned(4, {vertices, colours, faces, origin, sorted_vertices, member_begin, corner_ranges, sorted_corners,
+                                 out_vertices, out_colours}) && aligned(8, {sorted_keys}),
                "every pointer but out_choice must be aligned to 4 bytes, sorted_keys to 8");
   simplify_place_kernel<<<dim3((unsigned)div_up(num_clusters, 256 / SIMPLIFY_GROUP)), dim3(256), 0, (hipStream_t)stream>>>(
       vertices, colours, faces, (int32_t)num_vertices, 3 * num_faces, origin, cell_size, regularisation, quadric ? 1 : 0,
@@ -533,8 +518,8 @@ extern "C" int ms_mesh_simplify_faces(const int32_t* faces, int64_t num_vertices
   MS_CHECK_ARG(num_clusters >= 0 && num_clusters <= num_vertices, "0 <= K <= V expected");
   if (num_faces == 0) return 0;
   MS_CHECK_ARG(faces && out_faces && third_keys && values && keep && (vertex_cluster || num_vertices == 0), "null pointer");
-  MS_CHECK_ARG(simplify_aligned({faces, vertex_cluster, out_faces, third_keys, values}, 3), "every pointer but keep must be aligned to 4 bytes");
-  simplify_faces_kernel<<<simplify_grid(num_faces), dim3(256), 0, (hipStream_t)stream>>>(
+  MS_CHECK_ARG(aligned(4, {faces, vertex_cluster, out_faces, third_keys, values}), "every pointer but keep must be aligned to 4 bytes");
+  simplify_faces_kernel<<<mesh_grid(num_faces), dim3(256), 0, (hipStream_t)stream>>>(
       faces, (int32_t)num_vertices, num_faces, vertex_cluster, (int32_t)num_clusters, out_faces, third_keys, values, keep);
   MS_CHECK_LAUNCH();
   return 0;
@@ -546,8 +531,8 @@ extern "C" int ms_mesh_simplify_pair_keys(const int32_t* new_faces, const int32_
   MS_CHECK_ARG(shift >= 1 && shift <= 32, "1 <= shift <= 32 expected");
   if (num_faces == 0) return 0;
   MS_CHECK_ARG(new_faces && order && pair_keys, "null pointer");
-  MS_CHECK_ARG(simplify_aligned({new_faces, order}, 3) && simplify_aligned({pair_keys}, 7), "int32 pointers aligned to 4 bytes, pair_keys to 8");
-  simplify_pair_keys_kernel<<<simplify_grid(num_faces), dim3(256), 0, (hipStream_t)stream>>>(new_faces, order, num_faces, shift, pair_keys);
+  MS_CHECK_ARG(aligned(4, {new_faces, order}) && aligned(8, {pair_keys}), "int32 pointers aligned to 4 bytes, pair_keys to 8");
+  simplify_pair_keys_kernel<<<mesh_grid(num_faces), dim3(256), 0, (hipStream_t)stream>>>(new_faces, order, num_faces, shift, pair_keys);
   MS_CHECK_LAUNCH();
   return 0;
 }
@@ -557,8 +542,8 @@ extern "C" int ms_mesh_simplify_dedup(const int32_t* new_faces, const int32_t* o
   SIMPLIFY_CHECK_SIZES(0, num_faces);
   if (num_faces == 0) return 0;
   MS_CHECK_ARG(new_faces && order && keep, "null pointer");
-  MS_CHECK_ARG(simplify_aligned({new_faces, order}, 3), "new_faces and order must be aligned to 4 bytes");
-  simplify_dedup_kernel<<<simplify_grid(num_faces), dim3(256), 0, (hipStream_t)stream>>>(new_faces, order, num_faces, keep);
+  MS_CHECK_ARG(aligned(4, {new_faces, order}), "new_faces and order must be aligned to 4 bytes");
+  simplify_dedup_kernel<<<mesh_grid(num_faces), dim3(256), 0, (hipStream_t)stream>>>(new_faces, order, num_faces, keep);
   MS_CHECK_LAUNCH();
   return 0;
 }
@@ -569,8 +554,8 @@ extern "C" int ms_mesh_simplify_map(const int32_t* vertex_cluster, int64_t num_v
   MS_CHECK_ARG(num_clusters >= 0 && num_clusters <= num_vertices, "0 <= K <= V expected");
   if (num_vertices == 0) return 0;
   MS_CHECK_ARG(vertex_cluster && vertex_map && cluster_scan, "null pointer");
-  MS_CHECK_ARG(simplify_aligned({vertex_cluster, cluster_scan, vertex_map}, 3), "every pointer must be aligned to 4 bytes");
-  simplify_map_kernel<<<simplify_grid(num_vertices), dim3(256), 0, (hipStream_t)stream>>>(
+  MS_CHECK_ARG(aligned(4, {vertex_cluster, cluster_scan, vertex_map}), "every pointer must be aligned to 4 bytes");
+  simplify_map_kernel<<<mesh_grid(num_vertices), dim3(256), 0, (hipStream_t)stream>>>(
       vertex_cluster, (int32_t)num_vertices, cluster_scan, (int32_t)num_clusters, vertex_map);
   MS_CHECK_LAUNCH();
   return 0;

@@ -396,16 +396,13 @@ visibility_weights_kernel(const int64_t* __restrict__ indexes, const float* __re
 
 using namespace ms;
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // scalar groups read and write v row-wise like m; vector groups keep one float per point there
 static int pick_shape(int group_type, const GroupArgs& a) {
   const int d = a.d;
   if (group_type == 2) return S_V1_L4;
   // MS_OPTIM_VEC=0 in the environment (read once): 4-byte pieces everywhere, for A/B measurements of the 16-byte pieces
   static const bool allow_vec = [] { const char* e = getenv("MS_OPTIM_VEC"); return !(e && e[0] == '0'); }();
-  const bool vec = allow_vec && d % 4 == 0 && aligned16(a.param) && aligned16(a.grad) && aligned16(a.m) && aligned16(a.out_step) &&
-                   (group_type != 0 || aligned16(a.v));
+  const bool vec = allow_vec && d % 4 == 0 && aligned(16, {a.param, a.grad, a.m, a.out_step}) && (group_type != 0 || aligned(16, {a.v}));
   if (vec) return d == 4 ? S_V4_L1 : d <= 16 ? S_V4_L4 : d <= 64 ? S_V4_L16 : S_V4_L16_K4;
   return d == 1 ? S_V1_L1 : d <= 4 ? S_V1_L4 : d <= 16 ? S_V1_L16 : d <= 64 ? S_V1_L16_K4 : S_V1_L16_K16;
 }

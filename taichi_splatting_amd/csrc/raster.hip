@@ -625,7 +625,7 @@ extern "C" int ms_raster_fwd_split(const float* points7, const float* features, 
                                    int tile_row_begin, int tile_row_end, void* stream) {
   MS_CHECK_ARG(cfg && split_scratch && k_capacity >= 0 && k_capacity < (1ll << 31), "null pointer / k_capacity outside [0, 2^31)");
   MS_CHECK_ARG(split_min_run >= 0 && split_seg_len >= 0, "negative split parameter");
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(split_scratch) & 255) == 0, "split_scratch must be 256-byte aligned");
+  MS_CHECK_ARG(aligned(256, {split_scratch}), "split_scratch must be 256-byte aligned");
   if (!raster_uses_splat_rows(cfg, 3, MS_F32)) {
     set_error("ms_raster_fwd_split: float32 RGB, plain pdf, alpha blending, tile 8 / 16 / 32");
     return MS_ERR_UNSUPPORTED;
@@ -662,7 +662,7 @@ extern "C" int ms_splat_rows_pack(const float* points7, const float* depth, cons
   MS_CHECK_ARG(n >= 0, "n < 0");
   if (n == 0) return 0;
   MS_CHECK_ARG(points7 && colours3 && rows, "null pointer");
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(rows) & 63) == 0, "rows must be 64-byte aligned");
+  MS_CHECK_ARG(aligned(64, {rows}), "rows must be 64-byte aligned");
   splat_rows_pack_kernel<<<dim3((unsigned)div_up(n, 256)), dim3(256), 0, (hipStream_t)stream>>>(points7, depth, colours3, n, rows);
   MS_CHECK_LAUNCH();
   return 0;

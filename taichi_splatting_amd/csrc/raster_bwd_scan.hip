@@ -985,7 +985,7 @@ extern "C" int ms_raster_bwd_moments_split(const float* points7, const float* fe
   MS_CHECK_ARG(cfg && points7 && features && tile_ranges && image && grad_image && moments && split_scratch, "null pointer");
   MS_CHECK_ARG(k_capacity >= 0 && k_capacity < (1ll << 31), "k_capacity must be in [0, 2^31)");
   MS_CHECK_ARG(split_min_run >= 0 && split_seg_len >= 0, "negative split parameter");
-  MS_CHECK_ARG((reinterpret_cast<uintptr_t>(split_scratch) & 255) == 0, "split_scratch must be 256-byte aligned");
+  MS_CHECK_ARG(aligned(256, {split_scratch}), "split_scratch must be 256-byte aligned");
   // (the scratch is carved for the tile size: looked at here, before the launcher's own checks)
   if (cfg->tile_size != 8 && cfg->tile_size != 16 && cfg->tile_size != 32) {
     set_error("ms_raster_bwd_moments_split: tile_size must be 8, 16 or 32 (got %d)", cfg->tile_size);

@@ -32,16 +32,9 @@
 
 namespace ms {
 
-constexpr int RELOC_ROWS = 256;            // rows per workgroup = lanes per workgroup
-constexpr int RELOC_MAX_ARRAYS = 32;       // arrays per launch (a 3-D scene with Adam-like state has 17)
-constexpr int RELOC_UNROLL = 4;            // pieces in flight per lane
 constexpr int RELOC_COMPACT_BELOW = 8;     // a block with at most rows / 8 touched rows walks those alone
-constexpr int32_t DRAWN_BIT = 1 << 30;     // LDS encoding of a row: -1 untouched | source row (moved) | own row + DRAWN_BIT
-constexpr int64_t RELOC_MAX_ROW_BYTES = 1 << 20;
+constexpr int32_t DRAWN_BIT = ROW_FLAG_BIT;     // LDS encoding of a row: -1 untouched | source row (moved) | own row + DRAWN_BIT
 constexpr int MAX_RATIO = MS_RELOCATE_MAX_RATIO;
-
-typedef uint32_t __attribute__((may_alias)) piece4;
-typedef uint32_t __attribute__((ext_vector_type(4), may_alias)) piece16;
 
 // Counting rows into one device word: a same-address atomic costs about 12 ns at the L2, so one per wave (94 K waves at
 // 6 M rows) would take longer than the kernel's work.  The draw and fresh kernels therefore run a bounded grid with a
@@ -145,16 +138,11 @@ struct RelocArgs {
   const int32_t* count;
   int64_t n;
   int num_arrays;
-  RelocArray a[RELOC_MAX_ARRAYS];
+  RelocArray a[ROW_MAX_ARRAYS];
 };
 
-template <typename P> __device__ __forceinline__ P zero_piece();
-template <> __device__ __forceinline__ piece4 zero_piece<piece4>() { return 0u; }
-template <> __device__ __forceinline__ piece16 zero_piece<piece16>() { return piece16{0u, 0u, 0u, 0u}; }
-
-// The listed rows of the block in one array: pieces p = 0 .. listed * row_pieces - 1, lane t takes p = t, t + 256, ...;
-// (touched row, piece in row) advance by (256 / row_pieces, 256 % row_pieces) with one carry: no division in the loop.
-// Consecutive lanes take consecutive pieces of a row, and consecutive touched rows where rows are short.  All loads of a
+// The listed rows of the block in one array: pieces p = 0 .. listed * row_pieces - 1, lane t takes p = t, t + 256, ... and
+// follows its (touched row, piece in row) with a PieceWalk (rows.h).  Consecutive lanes take consecutive pieces of a row, and consecutive touched rows where rows are short.  All loads of a
 // round are issued before its first store.  Reads come from live rows (or `fresh`), writes go to dead rows or to the
 // lane's own row: no lane reads what another writes.
 template <typename P>
@@ -165,43 +153,41 @@ __device__ __forceinline__ void relocate_array(const RelocArray& a, const int32_
   const uint32_t action = a.flags & 3u;
   const P* from = reinterpret_cast<const P*>(action == ACTION_FRESH ? a.fresh : a.data);
   P* dst = reinterpret_cast<P*>(a.data) + first * (int64_t)ppr;
-  const uint32_t step_r = 256u / ppr, step_k = 256u % ppr;
-  uint32_t r = threadIdx.x / ppr, k = threadIdx.x % ppr;
+  PieceWalk w(threadIdx.x, ppr);
 #pragma unroll 1
-  for (uint32_t p = threadIdx.x; p < total; p += 256u * RELOC_UNROLL) {
-    P v[RELOC_UNROLL];
-    uint32_t at[RELOC_UNROLL];
-    bool write[RELOC_UNROLL];
+  for (uint32_t p = threadIdx.x; p < total; p += 256u * ROW_UNROLL) {
+    P v[ROW_UNROLL];
+    uint32_t at[ROW_UNROLL];
+    bool write[ROW_UNROLL];
 #pragma unroll
-    for (int u = 0; u < RELOC_UNROLL; ++u) {
+    for (int u = 0; u < ROW_UNROLL; ++u) {
       v[u] = zero_piece<P>();
       write[u] = false;
       at[u] = 0;
       if (p + 256u * u < total) {
-        const int32_t e = enc[r];
+        const int32_t e = enc[w.r];
         if (e >= 0 && (action != ACTION_COPY || !(e & DRAWN_BIT))) {
           write[u] = true;
-          at[u] = (uint32_t)row_of[r] * ppr + k;
-          if (action != ACTION_ZERO) v[u] = from[(int64_t)(e & (DRAWN_BIT - 1)) * (int64_t)ppr + k];
+          at[u] = (uint32_t)row_of[w.r] * ppr + w.k;
+          if (action != ACTION_ZERO) v[u] = from[(int64_t)(e & (DRAWN_BIT - 1)) * (int64_t)ppr + w.k];
         }
       }
-      r += step_r; k += step_k;
-      if (k >= ppr) { k -= ppr; ++r; }
+      w.advance();
     }
 #pragma unroll
-    for (int u = 0; u < RELOC_UNROLL; ++u)
+    for (int u = 0; u < ROW_UNROLL; ++u)
       if (write[u]) dst[at[u]] = v[u];
   }
 }
 
 __global__ void __launch_bounds__(256)
 relocate_move_kernel(RelocArgs m) {
-  __shared__ int32_t enc[RELOC_ROWS];        // the rows to walk (the touched ones in row order, or all): source | DRAWN_BIT, -1
-  __shared__ uint8_t row_of[RELOC_ROWS];     // ... and their row within the block
+  __shared__ int32_t enc[ROW_BLOCK];         // the rows to walk (the touched ones in row order, or all): source | DRAWN_BIT, -1
+  __shared__ uint8_t row_of[ROW_BLOCK];      // ... and their row within the block
   __shared__ int wave_touched[4];
-  const int64_t first = (int64_t)blockIdx.x * RELOC_ROWS;
+  const int64_t first = (int64_t)blockIdx.x * ROW_BLOCK;
   const int64_t left = m.n - first;
-  const int rows = left < RELOC_ROWS ? (int)left : RELOC_ROWS;
+  const int rows = left < ROW_BLOCK ? (int)left : ROW_BLOCK;
   int32_t e = -1;
   if ((int)threadIdx.x < rows) {
     const int64_t row = first + threadIdx.x;
@@ -248,40 +234,22 @@ relocate_move_kernel(RelocArgs m) {
 // of 3 words: no bank conflicts).  rotation is one 16-byte load per lane, alpha_logit one coalesced word.
 // 56 bytes per row in, 12 out.
 
-// total pieces of P from src to dst, lane t takes t, t + 256, ...
-template <typename P>
-__device__ __forceinline__ void copy_pieces(P* dst, const P* src, uint32_t total) {
-  for (uint32_t p = threadIdx.x; p < total; p += RELOC_ROWS) dst[p] = src[p];
-}
-
-// `bytes` (a multiple of 4) from src to dst; vec16: both 16-byte aligned
-__device__ __forceinline__ void copy_range(void* dst, const void* src, uint32_t bytes, bool vec16) {
-  if (vec16) {
-    const uint32_t n16 = bytes >> 4;
-    copy_pieces(reinterpret_cast<piece16*>(dst), reinterpret_cast<const piece16*>(src), n16);
-    copy_pieces(reinterpret_cast<piece4*>(dst) + n16 * 4, reinterpret_cast<const piece4*>(src) + n16 * 4,
-                (bytes & 15u) >> 2);
-  } else {
-    copy_pieces(reinterpret_cast<piece4*>(dst), reinterpret_cast<const piece4*>(src), bytes >> 2);
-  }
-}
-
 __device__ __forceinline__ float add_nonzero(float x, float off) { return off != 0.0f ? x + off : x; }
 
-__global__ void __launch_bounds__(RELOC_ROWS)
+__global__ void __launch_bounds__(ROW_BLOCK)
 perturb_positions_kernel(float* position, const float* __restrict__ log_scaling, const float* __restrict__ rotation,
                          const float* __restrict__ alpha_logit, const float* __restrict__ z, int64_t n, float step,
                          double k, double x0, int vec16) {
-  __shared__ __attribute__((aligned(16))) float lds_p[RELOC_ROWS * 3];
-  __shared__ __attribute__((aligned(16))) float lds_s[RELOC_ROWS * 3];
-  __shared__ __attribute__((aligned(16))) float lds_z[RELOC_ROWS * 3];
-  const int64_t first = (int64_t)blockIdx.x * RELOC_ROWS;
+  __shared__ __attribute__((aligned(16))) float lds_p[ROW_BLOCK * 3];
+  __shared__ __attribute__((aligned(16))) float lds_s[ROW_BLOCK * 3];
+  __shared__ __attribute__((aligned(16))) float lds_z[ROW_BLOCK * 3];
+  const int64_t first = (int64_t)blockIdx.x * ROW_BLOCK;
   const int64_t left = n - first;
-  const int rows = left < RELOC_ROWS ? (int)left : RELOC_ROWS;
+  const int rows = left < ROW_BLOCK ? (int)left : ROW_BLOCK;
   const uint32_t bytes = (uint32_t)rows * 12u;
-  copy_range(lds_p, position + first * 3, bytes, vec16 != 0);
-  copy_range(lds_s, log_scaling + first * 3, bytes, vec16 != 0);
-  copy_range(lds_z, z + first * 3, bytes, vec16 != 0);
+  copy_range<1>(lds_p, position + first * 3, bytes, vec16 != 0);
+  copy_range<1>(lds_s, log_scaling + first * 3, bytes, vec16 != 0);
+  copy_range<1>(lds_z, z + first * 3, bytes, vec16 != 0);
   __syncthreads();
   const int t = (int)threadIdx.x;
   if (t < rows) {
@@ -313,14 +281,12 @@ perturb_positions_kernel(float* position, const float* __restrict__ log_scaling,
     }
   }
   __syncthreads();
-  copy_range(position + first * 3, lds_p, bytes, vec16 != 0);
+  copy_range<1>(position + first * 3, lds_p, bytes, vec16 != 0);
 }
 
 }  // namespace ms
 
 using namespace ms;
-
-static bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 static int64_t count_grid(int64_t n) { const int64_t b = div_up(n, 256); return b < COUNT_BLOCKS ? b : COUNT_BLOCKS; }
 
@@ -333,9 +299,9 @@ extern "C" int ms_relocate_weights(const float* alpha_logit, int64_t n, float th
                                    int64_t* counts, void* stream) {
   const int rc = check_rows(n, "ms_relocate_weights");
   if (rc) return rc;
-  MS_CHECK_ARG(counts != nullptr && aligned_to(counts, 8), "counts: 3 int64 expected");
+  MS_CHECK_ARG(counts != nullptr && aligned(8, {counts}), "counts: 3 int64 expected");
   MS_CHECK_ARG(n == 0 || (alpha_logit && weights && count), "null pointer");
-  MS_CHECK_ARG(aligned_to(alpha_logit, 4) && aligned_to(weights, 8) && aligned_to(count, 4), "misaligned pointer");
+  MS_CHECK_ARG(aligned(4, {alpha_logit, count}) && aligned(8, {weights}), "misaligned pointer");
   MS_CHECK_ARG(!(threshold != threshold), "threshold is NaN");
   relocate_weights_kernel<<<dim3((unsigned)div_up(n > 3 ? n : 3, 256)), dim3(256), 0, (hipStream_t)stream>>>(
       alpha_logit, n, threshold, weights, count, counts);
@@ -349,8 +315,7 @@ extern "C" int ms_relocate_draw(const int64_t* weights, const int64_t* cdf, cons
   if (rc) return rc;
   if (n == 0) return 0;
   MS_CHECK_ARG(weights && cdf && random && src && count && counts, "null pointer");
-  MS_CHECK_ARG(aligned_to(weights, 8) && aligned_to(cdf, 8) && aligned_to(random, 8) && aligned_to(counts, 8) &&
-               aligned_to(src, 4) && aligned_to(count, 4), "misaligned pointer");
+  MS_CHECK_ARG(aligned(8, {weights, cdf, random, counts}) && aligned(4, {src, count}), "misaligned pointer");
   relocate_draw_kernel<<<dim3((unsigned)count_grid(n)), dim3(256), 0, (hipStream_t)stream>>>(weights, cdf, random, n, src,
                                                                                              count, counts);
   MS_CHECK_LAUNCH();
@@ -366,8 +331,8 @@ extern "C" int ms_relocate_fresh(const float* alpha_logit, const float* log_scal
   MS_CHECK_ARG(min_opacity > 0.0 && min_opacity < 1.0 - 1e-7, "0 < min_opacity < 1 - 1e-7 expected");
   if (n == 0) return 0;
   MS_CHECK_ARG(alpha_logit && log_scaling && count && binomials && fresh_opacity && fresh_scale && counts, "null pointer");
-  MS_CHECK_ARG(aligned_to(alpha_logit, 4) && aligned_to(log_scaling, 4) && aligned_to(count, 4) && aligned_to(binomials, 8) &&
-               aligned_to(fresh_opacity, 4) && aligned_to(fresh_scale, 4) && aligned_to(counts, 8), "misaligned pointer");
+  MS_CHECK_ARG(aligned(4, {alpha_logit, log_scaling, count, fresh_opacity, fresh_scale}) && aligned(8, {binomials, counts}),
+               "misaligned pointer");
   relocate_fresh_kernel<<<dim3((unsigned)count_grid(n)), dim3(256), 0, (hipStream_t)stream>>>(
       alpha_logit, log_scaling, scale_dims, count, n, min_opacity, binomials, fresh_opacity, fresh_scale, counts);
   MS_CHECK_LAUNCH();
@@ -382,23 +347,15 @@ extern "C" int ms_relocate_move(const ms_relocate_array* arrays, int num_arrays,
   // every descriptor is checked before the first launch: an error return leaves every array as it was
   for (int i = 0; i < num_arrays; ++i) {
     const ms_relocate_array& a = arrays[i];
-    if (a.struct_size != sizeof(ms_relocate_array)) {
-      set_error("ms_relocate_move: ms_relocate_array of another ABI (struct_size %u, this library: %u)", a.struct_size,
-                (unsigned)sizeof(ms_relocate_array));
-      return MS_ERR_ABI;
-    }
-    if (a.row_bytes <= 0 || a.row_bytes % 4 != 0 || a.row_bytes > RELOC_MAX_ROW_BYTES) {
-      set_error("ms_relocate_move: array %d: row_bytes must be a positive multiple of 4, at most %lld (got %lld)", i,
-                (long long)RELOC_MAX_ROW_BYTES, (long long)a.row_bytes);
-      return MS_ERR_BAD_ARG;
-    }
+    const int rc_row = check_row_array(__func__, i, a.struct_size, sizeof(ms_relocate_array), a.row_bytes);
+    if (rc_row) return rc_row;
     if (a.role < MS_RELOCATE_COPY || a.role > MS_RELOCATE_SCALE) {
       set_error("ms_relocate_move: array %d: unknown role %d", i, a.role);
       return MS_ERR_BAD_ARG;
     }
     const bool wants_fresh = a.role == MS_RELOCATE_OPACITY || a.role == MS_RELOCATE_SCALE;
     if (!a.data || (wants_fresh && !a.fresh)) { set_error("ms_relocate_move: array %d: null pointer", i); return MS_ERR_BAD_ARG; }
-    if (!aligned_to(a.data, 4) || (wants_fresh && !aligned_to(a.fresh, 4))) {
+    if (!aligned(4, {a.data, wants_fresh ? a.fresh : nullptr})) {
       set_error("ms_relocate_move: array %d: bases must be 4-byte aligned", i);
       return MS_ERR_BAD_ARG;
     }
@@ -411,17 +368,17 @@ extern "C" int ms_relocate_move(const ms_relocate_array* arrays, int num_arrays,
   MS_CHECK_ARG(src && count, "null source table");
   RelocArgs m{};
   m.src = src; m.count = count; m.n = n;
-  const dim3 grid((unsigned)div_up(n, RELOC_ROWS));
+  const dim3 grid((unsigned)div_up(n, ROW_BLOCK));
   for (int i = 0; i < num_arrays; ++i) {
     const ms_relocate_array& a = arrays[i];
     const bool wants_fresh = a.role == MS_RELOCATE_OPACITY || a.role == MS_RELOCATE_SCALE;
-    const bool vec = a.row_bytes % 16 == 0 && aligned_to(a.data, 16) && (!wants_fresh || aligned_to(a.fresh, 16));
     RelocArray& out = m.a[m.num_arrays++];
     out.data = (char*)a.data;
     out.fresh = wants_fresh ? (const char*)a.fresh : nullptr;
-    out.row_pieces = (uint32_t)(a.row_bytes / (vec ? 16 : 4));
-    out.flags = (wants_fresh ? ACTION_FRESH : a.role == MS_RELOCATE_ZERO_TOUCHED ? ACTION_ZERO : ACTION_COPY) | (vec ? 4u : 0u);
-    if (m.num_arrays == RELOC_MAX_ARRAYS || i == num_arrays - 1) {
+    const RowPieces pieces(a.row_bytes, {out.data, out.fresh});
+    out.row_pieces = pieces.row_pieces;
+    out.flags = (wants_fresh ? ACTION_FRESH : a.role == MS_RELOCATE_ZERO_TOUCHED ? ACTION_ZERO : ACTION_COPY) | (pieces.vec ? 4u : 0u);
+    if (m.num_arrays == ROW_MAX_ARRAYS || i == num_arrays - 1) {
       relocate_move_kernel<<<grid, dim3(256), 0, (hipStream_t)stream>>>(m);
       MS_CHECK_LAUNCH();
       m.num_arrays = 0;
@@ -437,10 +394,9 @@ extern "C" int ms_perturb_positions(float* position, const float* log_scaling, c
   MS_CHECK_ARG(step == step && k == k && x0 == x0, "step, k and x0 must not be NaN");
   if (n == 0) return 0;
   MS_CHECK_ARG(position && log_scaling && rotation && alpha_logit && z, "null pointer");
-  MS_CHECK_ARG(aligned_to(position, 4) && aligned_to(log_scaling, 4) && aligned_to(rotation, 4) && aligned_to(alpha_logit, 4) &&
-               aligned_to(z, 4), "misaligned pointer");
-  const int vec16 = aligned_to(position, 16) && aligned_to(log_scaling, 16) && aligned_to(rotation, 16) && aligned_to(z, 16);
-  perturb_positions_kernel<<<dim3((unsigned)div_up(n, RELOC_ROWS)), dim3(RELOC_ROWS), 0, (hipStream_t)stream>>>(
+  MS_CHECK_ARG(aligned(4, {position, log_scaling, rotation, alpha_logit, z}), "misaligned pointer");
+  const int vec16 = aligned(16, {position, log_scaling, rotation, z});
+  perturb_positions_kernel<<<dim3((unsigned)div_up(n, ROW_BLOCK)), dim3(ROW_BLOCK), 0, (hipStream_t)stream>>>(
       position, log_scaling, rotation, alpha_logit, z, n, step, k, x0, vec16);
   MS_CHECK_LAUNCH();
   return 0;

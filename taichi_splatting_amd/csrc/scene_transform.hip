@@ -29,11 +29,8 @@
 namespace ms {
 
 constexpr int XFORM_ROWS = MS_SCENE_XFORM_ROWS;   // rows per workgroup = lanes per workgroup = vectors per LDS chunk
-constexpr int XFORM_UNROLL = 4;                   // pieces in flight per lane
-static_assert(XFORM_ROWS == 256, "one lane per row of the block");
-
-typedef uint32_t __attribute__((may_alias)) piece4;
-typedef uint32_t __attribute__((ext_vector_type(4), may_alias)) piece16;
+constexpr int XFORM_UNROLL = 4;                   // pieces in flight per lane of the chunk copies (rows.h)
+static_assert(XFORM_ROWS == ROW_BLOCK, "one lane per row of the block");
 
 template <typename T>
 struct SceneXformArgs {
@@ -46,33 +43,6 @@ struct SceneXformArgs {
   double srt[12], ln_s, q[4];      // MS_SCENE_XFORM_* of the header, in double for the geometry
   T m[83];                         // M_1 (3x3) | M_2 (5x5) | M_3 (7x7), row-major
 };
-
-// total pieces of P from src to dst, lane t takes t, t + 256, ...; XFORM_UNROLL loads are issued before the first store
-template <typename P>
-__device__ __forceinline__ void copy_pieces(P* __restrict__ dst, const P* __restrict__ src, uint32_t total) {
-#pragma unroll 1
-  for (uint32_t p = threadIdx.x; p < total; p += XFORM_ROWS * XFORM_UNROLL) {
-    P v[XFORM_UNROLL];
-#pragma unroll
-    for (int u = 0; u < XFORM_UNROLL; ++u)
-      if (p + XFORM_ROWS * u < total) v[u] = src[p + XFORM_ROWS * u];
-#pragma unroll
-    for (int u = 0; u < XFORM_UNROLL; ++u)
-      if (p + XFORM_ROWS * u < total) dst[p + XFORM_ROWS * u] = v[u];
-  }
-}
-
-// `bytes` (a multiple of 4) from src to dst; vec16: both 16-byte aligned
-__device__ __forceinline__ void copy_range(void* dst, const void* src, uint32_t bytes, bool vec16) {
-  if (vec16) {
-    const uint32_t n16 = bytes >> 4;
-    copy_pieces(reinterpret_cast<piece16*>(dst), reinterpret_cast<const piece16*>(src), n16);
-    copy_pieces(reinterpret_cast<piece4*>(dst) + n16 * 4, reinterpret_cast<const piece4*>(src) + n16 * 4,
-                (bytes & 15u) >> 2);
-  } else {
-    copy_pieces(reinterpret_cast<piece4*>(dst), reinterpret_cast<const piece4*>(src), bytes >> 2);
-  }
-}
 
 __device__ __forceinline__ float xf_fma(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double xf_fma(double a, double b, double c) { return fma(a, b, c); }
@@ -159,7 +129,7 @@ scene_transform_kernel(const SceneXformArgs<T> a) {
     for (int64_t v0 = v_begin; v0 < v_end; v0 += XFORM_ROWS) {
       const int count = v_end - v0 < XFORM_ROWS ? (int)(v_end - v0) : XFORM_ROWS;
       const uint32_t bytes = (uint32_t)count * (uint32_t)(K * sizeof(T));
-      copy_range(lds, a.feature + v0 * K, bytes, vec16);
+      copy_range<XFORM_UNROLL>(lds, a.feature + v0 * K, bytes, vec16);
       __syncthreads();
       if ((int)threadIdx.x < count) {
         T* c = lds + threadIdx.x * K;      // this lane's vector: nobody else touches it between the two barriers
@@ -171,7 +141,7 @@ scene_transform_kernel(const SceneXformArgs<T> a) {
         lds_vector<T, K>(v, c, true);
       }
       __syncthreads();
-      copy_range(a.out_feature + v0 * K, lds, bytes, vec16);
+      copy_range<XFORM_UNROLL>(a.out_feature + v0 * K, lds, bytes, vec16);
       __syncthreads();                     // the next chunk's loads overwrite the LDS image
     }
   }
@@ -194,7 +164,7 @@ static int scene_transform_typed(const void* position, void* out_position, const
   a.rotation = (const T*)rotation; a.out_rotation = (T*)out_rotation;
   a.feature = (const T*)feature; a.out_feature = (T*)out_feature;
   a.n = n; a.f = f;
-  a.vec16 = ((reinterpret_cast<uintptr_t>(feature) | reinterpret_cast<uintptr_t>(out_feature)) & 15) == 0;
+  a.vec16 = aligned(16, {feature, out_feature});
   for (int k = 0; k < 12; ++k) a.srt[k] = t[MS_SCENE_XFORM_SRT + k];
   a.ln_s = t[MS_SCENE_XFORM_LN_S];
   for (int k = 0; k < 4; ++k) a.q[k] = t[MS_SCENE_XFORM_QUAT + k];
@@ -229,11 +199,8 @@ extern "C" int ms_scene_transform(const void* position, void* out_position, cons
     if (f < 1 || f > (1 << 20)) { set_error("ms_scene_transform: 1 <= f <= 2^20 expected (got %d)", f); return MS_ERR_BAD_ARG; }
   }
   MS_CHECK_ARG(transform_host != nullptr, "transform_host is null");
-  const uintptr_t mask = dtype == MS_F64 ? 7 : 3;
-  const void* all[8] = {position, out_position, log_scaling, out_log_scaling, rotation, out_rotation, feature, out_feature};
-  uintptr_t bits = 0;
-  for (const void* p : all) bits |= reinterpret_cast<uintptr_t>(p);
-  MS_CHECK_ARG((bits & mask) == 0, "every pointer must be aligned to its element type");
+  MS_CHECK_ARG(aligned(dtype == MS_F64 ? 8 : 4, {position, out_position, log_scaling, out_log_scaling, rotation, out_rotation,
+                                                 feature, out_feature}), "every pointer must be aligned to its element type");
   if (n == 0 || !(position || log_scaling || rotation || feature)) return 0;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == MS_F32)

@@ -451,7 +451,7 @@ int sh_fwd_inplace_launch(const void* params, const void* positions, const void*
   if (active_degree < 0 || active_degree > degree) { set_error("sh_fwd_inplace_launch: active degree outside [0, degree]"); return MS_ERR_BAD_ARG; }
   if (splat_rows && !(dtype == MS_F32 && f == 3)) { set_error("sh_fwd_inplace_launch: splat rows are float32 RGB"); return MS_ERR_BAD_ARG; }
   static const bool rows_off = [] { const char* e = getenv("MS_SH_FWD"); return e && e[0] == 'w'; }();   // "walk": the per-lane row walk
-  if (dtype == MS_F32 && f == 3 && degree == 3 && active_degree == 3 && !rows_off && (reinterpret_cast<uintptr_t>(params) & 15) == 0) {
+  if (dtype == MS_F32 && f == 3 && degree == 3 && active_degree == 3 && !rows_off && aligned(16, {params})) {
     int64_t blocks = div_up(n, 256);
     constexpr int64_t ROWS_BLOCKS = 16384;
     if (blocks > ROWS_BLOCKS) blocks = ROWS_BLOCKS;       // grid-stride: a resident grid streams best

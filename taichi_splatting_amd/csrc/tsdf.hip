@@ -457,11 +457,8 @@ extern "C" int ms_tsdf_integrate(float* tsdf, float* weight, float* colour, int 
   MS_CHECK_ARG(width >= 1 && height >= 1 && (int64_t)width * height < ((int64_t)1 << 31), "image of 1 .. 2^31 - 1 pixels expected");
   MS_CHECK_ARG(tsdf && weight && depth && cameras, "null tsdf, weight, depth or cameras");
   MS_CHECK_ARG((colour == nullptr) == (image == nullptr), "a coloured volume needs colour images, a plain one takes none");
-  const uintptr_t wide = reinterpret_cast<uintptr_t>(tsdf) | reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(colour);
-  MS_CHECK_ARG((wide & 15) == 0, "tsdf, weight and colour must be aligned to 16 bytes");
-  const uintptr_t narrow = reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(pixel_weight) |
-                           reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(cameras);
-  MS_CHECK_ARG((narrow & 3) == 0, "depth, pixel_weight, image and cameras must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(16, {tsdf, weight, colour}), "tsdf, weight and colour must be aligned to 16 bytes");
+  MS_CHECK_ARG(aligned(4, {depth, pixel_weight, image, cameras}), "depth, pixel_weight, image and cameras must be aligned to 4 bytes");
   const int n = nx * ny * nz;
   const TsdfGrid g = tsdf_grid(nx, ny, nz, origin_host, voxel_size);
   tsdf_integrate_kernel<<<dim3((unsigned)div_up(div_up(n, TSDF_RUN), 256)), dim3(256), 0, (hipStream_t)stream>>>(
@@ -476,9 +473,7 @@ extern "C" int ms_tsdf_classify(const float* tsdf, const float* weight, int nx, 
   MS_CHECK_ARG(tsdf_grid_ok(nx, ny, nz), "dims >= 1 with nx ny nz <= 2^27 expected");
   MS_CHECK_ARG(min_weight == min_weight, "NaN min_weight");
   MS_CHECK_ARG(tsdf && weight && word && vertex_count && triangle_count, "null pointer");
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(tsdf) | reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(word) |
-                         reinterpret_cast<uintptr_t>(vertex_count) | reinterpret_cast<uintptr_t>(triangle_count);
-  MS_CHECK_ARG((bits & 3) == 0, "every pointer must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {tsdf, weight, word, vertex_count, triangle_count}), "every pointer must be aligned to 4 bytes");
   const int n = nx * ny * nz;
   const double zero[3] = {0.0, 0.0, 0.0};
   tsdf_classify_kernel<<<dim3((unsigned)div_up(n, 256)), dim3(256), 0, (hipStream_t)stream>>>(
@@ -498,11 +493,8 @@ extern "C" int ms_tsdf_emit(const float* tsdf, const float* weight, const float*
   MS_CHECK_ARG(tsdf && weight && word && vertex_scan && triangle_scan, "null pointer");
   MS_CHECK_ARG(out_vertices && out_faces, "null output (an empty mesh needs no emit call)");
   MS_CHECK_ARG(out_colours == nullptr || colour != nullptr, "out_colours needs a coloured volume");
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(tsdf) | reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(colour) |
-                         reinterpret_cast<uintptr_t>(word) | reinterpret_cast<uintptr_t>(vertex_scan) |
-                         reinterpret_cast<uintptr_t>(triangle_scan) | reinterpret_cast<uintptr_t>(out_vertices) |
-                         reinterpret_cast<uintptr_t>(out_faces) | reinterpret_cast<uintptr_t>(out_colours);
-  MS_CHECK_ARG((bits & 3) == 0, "every pointer must be aligned to 4 bytes");
+  MS_CHECK_ARG(aligned(4, {tsdf, weight, colour, word, vertex_scan, triangle_scan, out_vertices, out_faces, out_colours}),
+               "every pointer must be aligned to 4 bytes");
   const int n = nx * ny * nz;
   tsdf_emit_kernel<<<dim3((unsigned)div_up(n, 256)), dim3(256), 0, (hipStream_t)stream>>>(
       tsdf, weight, colour, tsdf_grid(nx, ny, nz, origin_host, voxel_size), n, (float)min_weight, word, vertex_scan,

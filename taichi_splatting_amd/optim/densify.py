@@ -18,6 +18,7 @@ from typing import Callable, Dict, Iterable, List, Optional, Tuple
 import torch
 
 from .. import _lib
+from .parameter_class import per_point_arrays
 
 _pinned_counts: Dict[torch.device, torch.Tensor] = {}
 
@@ -99,7 +100,7 @@ def move_rows(plan: DensifyPlan, arrays: List[Tuple[torch.Tensor, bool]]) -> Lis
     d.struct_size = ctypes.sizeof(_lib.DensifyArrayC)
     d.child_fill = int(bool(copy_parent))
     d.src, d.dst = src.data_ptr(), out.data_ptr()
-    d.row_bytes = (src.numel() // plan.n) * src.element_size()
+    d.row_bytes = _lib.row_bytes(src, plan.n)
   _lib.check(_lib.load().ms_densify_move(descriptors, len(arrays), plan.src_row.data_ptr(), plan.child_slot.data_ptr(),
                                          plan.n, plan.n_out, _lib.current_stream(device)), "densify move")
   return outputs
@@ -148,18 +149,12 @@ def densify(params, prune_mask: torch.Tensor, split_mask: torch.Tensor, children
   if plan.n_out == 0:
     raise ValueError("densify: no rows left (every point pruned)")
 
-  names = list(params.tensors.keys())
-  tensor_state = params.tensor_state
-  state_keys = [(name, key) for name, st in tensor_state.items() for key in st]
-  for name, key in state_keys:
-    assert tensor_state[name][key].shape[:1] == (n,), \
-      f"optimiser state {name}.{key} is not per point: shape {tuple(tensor_state[name][key].shape)}"
-  arrays = [(params.tensors[name], True) for name in names]
-  arrays += [(tensor_state[name][key], key in inherit_state) for name, key in state_keys]
-  moved = move_rows(plan, arrays)
+  names, state_keys, arrays = per_point_arrays(params)
+  copy_parent = [True] * len(names) + [key in inherit_state for _, key in state_keys]
+  moved = move_rows(plan, list(zip(arrays, copy_parent)))
 
   tensors = dict(zip(names, moved[:len(names)]))
-  new_state: Dict[str, Dict[str, torch.Tensor]] = {name: {} for name in tensor_state}
+  new_state: Dict[str, Dict[str, torch.Tensor]] = {name: {} for name in params.tensor_state}
   for (name, key), t in zip(state_keys, moved[len(names):]):
     new_state[name][key] = t
 

@@ -32,6 +32,20 @@ def replace_dict(d, **kwargs):
   return d
 
 
+def per_point_arrays(params: 'ParameterClass'):
+  """Every per-point array of ``params``, as ``(names, state_keys, tensors)``: ``tensors`` holds the tensors in the
+  order of ``names``, then the optimiser state tensors in the order of ``state_keys`` (``(name, key)`` pairs).  Every
+  state tensor must have one row per point."""
+  names = list(params.tensors.keys())
+  n = params.tensors[names[0]].shape[0]
+  tensor_state = params.tensor_state
+  state_keys = [(name, key) for name, st in tensor_state.items() for key in st]
+  for name, key in state_keys:
+    t = tensor_state[name][key]
+    assert t.shape[:1] == (n,), f"optimiser state {name}.{key} is not per point: shape {tuple(t.shape)}"
+  return names, state_keys, [params.tensors[name] for name in names] + [tensor_state[name][key] for name, key in state_keys]
+
+
 class ParameterClass:
   """
   Parameters:

@@ -21,6 +21,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from .. import _lib
+from .parameter_class import per_point_arrays
 
 _binomials: Dict[torch.device, torch.Tensor] = {}
 
@@ -107,7 +108,7 @@ def relocate_arrays(alpha_logit: torch.Tensor, log_scaling: torch.Tensor, arrays
     d.struct_size = ctypes.sizeof(_lib.RelocateArrayC)
     d.role = int(role)
     d.data = t.data_ptr()
-    d.row_bytes = (t.numel() // n) * t.element_size()
+    d.row_bytes = _lib.row_bytes(t, n)
     if role in (_lib.RELOCATE_OPACITY, _lib.RELOCATE_SCALE):
       fresh = fresh_opacity if role == _lib.RELOCATE_OPACITY else fresh_scale
       assert t.dtype == torch.float32 and t.numel() == fresh.numel(), "relocate: opacity / scale role on a tensor of another shape"
@@ -139,25 +140,19 @@ def relocate(params, *, min_opacity: float = 0.005, random: Optional[torch.Tenso
   ``random``: (N,) int64 read as unsigned words, default ``torch.randint`` over the int64 range.  Storage, optimiser and
   row count stay as they are and nothing is read back to the host: the call can be captured into a graph (after one
   call outside a capture, which uploads the binomial table).  Gradients (``.grad``) are not touched."""
-  names = list(params.tensors.keys())
   for key in (opacity, scale):
     if key not in params.tensors:
-      raise KeyError(f"relocate: no tensor {key!r} in {names}")
+      raise KeyError(f"relocate: no tensor {key!r} in {list(params.tensors.keys())}")
   logit_threshold(min_opacity)
   inherit_state = set(inherit_state)
-  n = params.tensors[names[0]].shape[0]
-  _check_random(random, n)
+  _check_random(random, next(iter(params.tensors.values())).shape[0])
   _lib.require_gpu(*params.tensors.values())
 
-  tensor_state = params.tensor_state
-  arrays: List[Tuple[torch.Tensor, int]] = []
+  names, state_keys, tensors = per_point_arrays(params)
+  roles = [_lib.RELOCATE_OPACITY if name == opacity else _lib.RELOCATE_SCALE if name == scale else _lib.RELOCATE_COPY
+           for name in names]
+  roles += [_lib.RELOCATE_INHERIT if key in inherit_state else _lib.RELOCATE_ZERO_TOUCHED for _, key in state_keys]
   with torch.no_grad():
-    for name in names:
-      role = _lib.RELOCATE_OPACITY if name == opacity else _lib.RELOCATE_SCALE if name == scale else _lib.RELOCATE_COPY
-      arrays.append((params.tensors[name].detach(), role))
-    for name, st in tensor_state.items():
-      for key, t in st.items():
-        assert t.shape[:1] == (n,), f"optimiser state {name}.{key} is not per point: shape {tuple(t.shape)}"
-        arrays.append((t, _lib.RELOCATE_INHERIT if key in inherit_state else _lib.RELOCATE_ZERO_TOUCHED))
+    arrays = [(t.detach(), role) for t, role in zip(tensors, roles)]
     return relocate_arrays(params.tensors[opacity].detach(), params.tensors[scale].detach(), arrays,
                            min_opacity=min_opacity, random=random)

@@ -182,6 +182,29 @@ def test_row_widths_of_every_residue_and_an_unaligned_source():
     assert torch.equal(zeroed, torch.cat([src[keep], torch.zeros_like(children)]))
 
 
+@pytest.mark.parametrize('children', [1, 3])
+def test_rows_wider_than_a_block(children):
+  """Rows of 255 .. 1024 pieces (tests/wide_rows.py): a lane's walk starts in row 0 and carries at most once per step.
+  Expected rows by torch indexing on copies of the inputs, compared on the bits."""
+  from taichi_splatting_amd.optim.densify import move_rows, plan_densify
+  from tests.wide_rows import N, bits, wide_arrays
+  arrays = wide_arrays(DEV)
+  before = {name: t.clone() for name, t in arrays.items()}
+  prune, split = masks('mixed', N, seed=children)
+  keep, split_only = ~(prune | split), split & ~prune
+  plan = plan_densify(prune, split, children)
+  assert plan.n_out == int(keep.sum()) + children * int(split_only.sum()) and plan.n_split > 0 and plan.n_kept > 0
+  moved = move_rows(plan, [(t, fill) for t in arrays.values() for fill in (True, False)])
+  torch.cuda.synchronize()
+  for i, (name, t) in enumerate(arrays.items()):
+    assert torch.equal(bits(t), bits(before[name])), name                     # the sources are read only
+    parents = before[name][split_only].repeat_interleave(children, dim=0)
+    copied, zeroed = moved[2 * i], moved[2 * i + 1]
+    assert copied.shape == zeroed.shape == (plan.n_out, t.shape[1]), name
+    assert torch.equal(bits(copied), bits(torch.cat([before[name][keep], parents]))), name
+    assert torch.equal(bits(zeroed), bits(torch.cat([before[name][keep], torch.zeros_like(parents)]))), name
+
+
 def deviations(fields, kernel, f32, f64, label):
   """Asserts |kernel - f64| <= 4 d32 with d32 = max |f32 - f64| per field; prints both."""
   for k in fields:

@@ -161,6 +161,53 @@ def test_two_runs_with_the_same_words_give_identical_bits(n):
   assert not torch.equal(r1.src, r3.src)
 
 
+@pytest.mark.parametrize('population', ['few_touched', 'many_touched'])
+def test_rows_wider_than_a_block(population):
+  """Rows of 255 .. 1024 pieces (tests/wide_rows.py) in every plain role, through both walks of the move: a block with
+  at most one touched row in 8 walks its touched rows alone (RELOC_COMPACT_BELOW of csrc/relocate.hip), any other block
+  all its rows.  Expected rows by torch indexing on copies of the inputs, compared on the bits."""
+  from taichi_splatting_amd.optim.relocate import relocate_arrays
+  from tests.wide_rows import N, bits, wide_arrays
+  g = torch.Generator().manual_seed(11)
+  alpha = (2.0 * torch.randn(N, generator=g)).clamp(-4.0, 12.0)
+  dead = torch.zeros(N, dtype=torch.bool)
+  if population == 'few_touched':
+    dead[[3, 100, 200, 270]] = True           # with their sources at most 8 touched rows of 256 and 5 of 44
+  else:
+    dead[::3] = True                          # a third of every block, before any source
+  alpha[dead] = -10.0
+  random = torch.randint(torch.iinfo(torch.int64).min, torch.iinfo(torch.int64).max, (N,), generator=g)
+  log_scaling = torch.randn(N, 3, generator=g)
+
+  roles = (COPY, ZERO, INHERIT)
+  arrays = {(name, role): t for role in roles for name, t in wide_arrays(DEV).items()}
+  before = {key: t.clone() for key, t in arrays.items()}
+  result = relocate_arrays(alpha.reshape(N, 1).to(DEV), log_scaling.to(DEV), [(t, role) for (_, role), t in arrays.items()],
+                           min_opacity=MIN_OPACITY, random=random.to(DEV))
+  torch.cuda.synchronize()
+
+  src, count, _ = oracle.draw(result.weights.cpu().numpy(), random.numpy().astype(np.uint64))
+  assert np.array_equal(result.src.cpu().numpy(), src) and np.array_equal(result.count.cpu().numpy(), count)
+  moved, touched = src != np.arange(N), (src != np.arange(N)) | (count > 0)
+  assert np.array_equal(moved, dead.numpy())
+  per_block = [(int(touched[b:b + 256].sum()), len(touched[b:b + 256])) for b in range(0, N, 256)]
+  assert [rows for _, rows in per_block] == [256, 44]
+  print(f"{population}: touched rows per block {per_block}")
+  if population == 'few_touched':
+    assert all(0 < t and t * 8 <= rows for t, rows in per_block), per_block          # the compact walk, in both blocks
+  else:
+    assert all(t * 8 > rows for t, rows in per_block), per_block                      # the full walk, in both blocks
+
+  t_src, t_moved, t_touched = (torch.from_numpy(x).to(DEV) for x in (src.astype(np.int64), moved, touched))
+  for (name, role), t in arrays.items():
+    want = before[(name, role)].clone()
+    if role == ZERO:
+      want[t_touched] = 0.0
+    else:
+      want[t_moved] = before[(name, role)][t_src[t_moved]]
+    assert torch.equal(bits(t), bits(want)), (name, role)
+
+
 # ---- position noise ---------------------------------------------------------------------------------------------------
 
 def noise_scene(n, seed=0):
