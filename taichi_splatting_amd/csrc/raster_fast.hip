@@ -299,7 +299,10 @@ split_plan_kernel(const int32_t* __restrict__ ranges, int tile_begin, int num_ti
   if (run <= min_run) return;
   int nseg = (run + seg_len - 1) / seg_len;
   if (nseg > SPLIT_MAX_SEG) nseg = SPLIT_MAX_SEG;
-  const int seg = ((run + nseg - 1) / nseg + 255) & ~255;
+  // equal segments, rounded up to the batch multiple — and never below seg_len: a run just above a multiple of seg_len
+  // (1025 entries at seg_len 1024; 16 385 at tile 32's default of 4096) otherwise came out as segments of 768 / 3328
+  int seg = ((run + nseg - 1) / nseg + 255) & ~255;
+  if (seg < seg_len) seg = seg_len;
   nseg = (run + seg - 1) / seg;
   const int first = atomicAdd(&counts[0], nseg), li = atomicAdd(&counts[1], 1);
   // the capacities are upper bounds when k_capacity >= K; otherwise the whole plan is void (the kernels that read it
