@@ -654,6 +654,33 @@ int ms_knn_points(const float* points3, const int32_t* order, int64_t n, int k,
                   float* out_dist2, int32_t* out_index /* may be NULL */, int64_t* out_stats /* may be NULL */,
                   void* tmp, size_t* tmp_bytes, void* stream);
 
+/* ---- k nearest points of ANOTHER set (csrc/knn_query.hip; an addition: Chamfer distance and F-score of a mesh against a
+ * ground-truth cloud, colour transfer between clouds, "farther than d from the surface") ----
+ * Exact: out_dist2 (N, k) float32 = the k smallest squared distances from queries3[i] (N, 3 float32) to the M rows of
+ * points3 (M, 3 float32), ascending; out_index (N, k) = the points' original indices; both rows are written at the
+ * query's ORIGINAL index.  Nothing is excluded: a query that coincides with a point finds it at distance 0.  With M < k
+ * the missing entries are +inf / -1; M == 0 (every entry missing) and N == 0 (no launch) are legal.  1 <= k <= 8,
+ * M, N < 2^31.  d2 is the function of ms_knn_points, (dx dx + dy dy) + dz dz on float32 differences, unfused: a distance
+ * is a pure function of its pair, so out_dist2 is bitwise independent of point_order, query_order and query_hint; under
+ * ties any valid index may be returned.
+ * point_order (M) and query_order (N): permutations (device), normally the Morton argsorts of the two sets on ONE grid
+ * (ms_morton_codes64 with the common bounding box + ms_radix_sort_pairs).  Runs of MS_KNN_BLOCK points in point_order are
+ * the blocks whose boxes prune the search; the 64 queries of a wave are consecutive in query_order.  query_hint: NULL,
+ * or (N) int32 where query_hint[i] is the position in point_order near which the query at position i of query_order
+ * should start (normally searchsorted(sorted point codes, sorted query codes)); it is clamped to 0 .. M - 1, and a wave
+ * seeds from the block of its middle active lane's hint.  NULL stands for i M / N.  Every block is still considered and
+ * every pruning test is <=: orders and hint decide the speed only (an order entry outside its range is clamped: wrong
+ * results, no stray access).
+ * out_stats: NULL, or a device int64[2] to which the search ADDS [blocks scanned x queries of the wave, point-query
+ * distance evaluations] (the caller zeroes it); brute force would evaluate M N.
+ * (tmp, tmp_bytes): see Conventions (sized by M; aligned to 16 bytes).  No host read, allocation or synchronisation:
+ * capturable into a graph.  MS_ERR_BAD_ARG names the argument: m or n < 0 or >= 2^31, k, a null points3 / point_order
+ * with m > 0, a null queries3 / query_order / out_dist2 with n > 0, null tmp_bytes. */
+int ms_knn_query(const float* points3, const int32_t* point_order, int64_t m,
+                 const float* queries3, const int32_t* query_order, const int32_t* query_hint /* may be NULL */, int64_t n,
+                 int k, float* out_dist2, int32_t* out_index /* may be NULL */, int64_t* out_stats /* may be NULL */,
+                 void* tmp, size_t* tmp_bytes, void* stream);
+
 /* ---- camera position ----------------------------------------------------------------------------------
  * out_position3 = inverse(T_camera_world)[0:3, 3] for a row-major 4x4 (perspective/params.py:62-65), one
  * launch instead of a device-side LU. */
@@ -1271,6 +1298,37 @@ int ms_mesh_simplify_dedup(const int32_t* new_faces, const int32_t* order, int64
 /* cluster_scan (K + 1): vertex_scan of ms_mesh_select_plan over the K clusters */
 int ms_mesh_simplify_map(const int32_t* vertex_cluster, int64_t num_vertices, const int32_t* cluster_scan,
                          int64_t num_clusters, int32_t* vertex_map, void* stream);
+
+/* ---- Surface samples of a mesh (csrc/mesh_sample.hip; an addition: what a mesh is scored through) -----------------------
+ * Uniform over the surface, area-weighted, stratified and seeded.  Meshes are as above.  No atomics on data, no host read,
+ * no scratch block; two runs give bitwise-equal outputs; both calls capture into a graph.
+ *
+ * ms_mesh_face_areas: area[f] (T float64) = 0.5 |(b - a) x (c - a)| with (a, b, c) the positions of face f: differences,
+ * products and the sum of squares (x x + y y) + z z are FLOAT64 operations on the float32 positions, without FMA
+ * contraction.  status (1 int32, device; zeroed by the call) receives 0 or a sum of MS_MESH_BAD_INDEX (a face index
+ * outside 0 .. V - 1; nothing is read through it) and MS_MESH_NOT_FINITE (a referenced vertex with a NaN or an infinity);
+ * such a face gets area 0.  The caller makes the inclusive cumulative sum cdf (T float64) of the areas.
+ *
+ * ms_mesh_sample_points, for sample i of n (n < 2^31), with cdf[T - 1] > 0:
+ *   t_i  = min((i + u0) (cdf[T - 1] / n), nextafter(cdf[T - 1], 0))        in float64: stratum i of n equal shares of area
+ *   face = the first f with cdf[f] > t_i (a binary search): a face of area 0 is never drawn
+ *   r = sqrt(u1), (wa, wb, wc) = (1 - r, r (1 - u2), r u2)                 in float32, sqrt correctly rounded
+ *   out_points[i] = (wa A + wb B) + wc C per component                     in float32, without FMA contraction
+ * out_face (n int32) and out_bary (n, 3) receive face and (wa, wb, wc); out_colours / out_normals (n, 3) the same
+ * combination of the three rows of colours / normals (normals are NOT renormalised).  With normals == NULL, out_normals
+ * is the unit face normal (b - a) x (c - a) / |.|, float64 rounded once.  Each of the four may be NULL.
+ * RANDOM NUMBERS are counter-based, a function of (seed, i, j) alone, j = 0, 1, 2:
+ *   mix(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16      on uint32
+ *   word(seed, i, j) = mix((uint32)i + mix((uint32)seed + 0x9e3779b9 (j + 1)))
+ *   u_j = (word(seed, i, j) >> 8) 2^-24                                       24 bits in [0, 1): exact in float32
+ * MS_ERR_BAD_ARG: sizes out of range, a null required pointer, n > 0 with V == 0 or T == 0, out_colours without colours. */
+int ms_mesh_face_areas(const float* vertices, const int32_t* faces, int64_t num_vertices, int64_t num_faces,
+                       double* area, int32_t* status, void* stream);
+int ms_mesh_sample_points(const float* vertices, const int32_t* faces, const float* colours /* may be NULL */,
+                          const float* normals /* may be NULL */, int64_t num_vertices, int64_t num_faces, const double* cdf,
+                          int64_t n, int64_t seed, float* out_points, int32_t* out_face /* may be NULL */,
+                          float* out_bary /* may be NULL */, float* out_colours /* may be NULL */,
+                          float* out_normals /* may be NULL */, void* stream);
 
 #ifdef __cplusplus
 }

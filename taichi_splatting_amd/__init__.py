@@ -19,7 +19,7 @@ from . import optim
 from .perspective import CameraParams
 from .taichi_queue import TaichiQueue, taichi_queue, queued
 from .loss import l1_ssim_loss, ssim
-from .scene_io import load_ply, save_ply, read_ply_header
+from .scene_io import load_ply, save_ply, read_ply_header, load_points_ply
 from .misc.coverage import camera_coverage, pack_cameras, Coverage
 from .misc.relocate import relocate_gaussians3d, perturb_positions
 from .optim.relocate import relocate, RelocateResult
@@ -31,6 +31,9 @@ from .geometry import gaussian_normals, render_geometry, GeometryImages, normal_
 from .fusion import TSDFVolume, TriangleMesh, save_mesh_ply, fuse_scene
 from .mesh import (MeshComponents, mesh_components, select_faces, remove_small_components, vertex_normals,
                    vertex_normal_sums, with_vertex_normals, simplify_mesh)
+from .misc.knn import knn_query
+from .mesh_eval import (SurfaceSamples, SurfaceMetrics, face_area_cdf, sample_mesh_points, surface_distances,
+                        surface_metrics, metrics_from_distances, evaluate_mesh)
 
 __version__ = '0.5.1'       # = MS_VERSION 501 of include/mi355_splat.h (tests/test_abi.py holds the two together)
 
@@ -53,6 +56,8 @@ __all__ = [
   'TSDFVolume', 'TriangleMesh', 'save_mesh_ply', 'fuse_scene',
   'MeshComponents', 'mesh_components', 'select_faces', 'remove_small_components', 'vertex_normals', 'vertex_normal_sums',
   'with_vertex_normals', 'simplify_mesh',
+  'knn_query', 'SurfaceSamples', 'SurfaceMetrics', 'face_area_cdf', 'sample_mesh_points', 'surface_distances',
+  'surface_metrics', 'metrics_from_distances', 'evaluate_mesh', 'load_points_ply',
 ]
 
 
@@ -65,7 +70,7 @@ def install_as_taichi_splatting():
   for sub in ('data_types', 'scene_io', 'renderer', 'rendering', 'taichi_queue', 'spherical_harmonics',
               'perspective', 'perspective.params',
               'perspective.projection', 'mapper', 'mapper.tile_mapper', 'rasterizer',
-              'rasterizer.function', 'rasterizer.wide', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'geometry', 'fusion', 'mesh', 'optim', 'optim.fractional', 'optim.relocate',
+              'rasterizer.function', 'rasterizer.wide', 'cuda_lib', 'misc', 'misc.renderer2d', 'misc.morton_sort', 'misc.knn', 'misc.coverage', 'misc.relocate', 'misc.kmeans', 'scene_codec', 'appearance', 'geometry', 'fusion', 'mesh', 'mesh_eval', 'optim', 'optim.fractional', 'optim.relocate',
               'optim.visibility_aware', 'optim.parameter_class', 'optim.util', 'benchmarks', 'benchmarks.util',
               'benchmarks.bench_projection', 'benchmarks.bench_rasterizer', 'benchmarks.bench_tilemapper',
               'benchmarks.bench_sh', 'examples',

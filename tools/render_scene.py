@@ -13,7 +13,8 @@ gaussians and tile overlaps; ms per frame is the median over the views after one
                                            [--coverage] [--sh-codes K [--coded]]
                                            [--mesh out.ply --voxel-size s [--bounds x0 y0 z0 x1 y1 z1]
                                             [--min-component-faces N] [--keep-components K] [--mesh-cell-size s]
-                                            [--mesh-normals]]
+                                            [--mesh-normals]
+                                            [--eval-points gt.ply --eval-threshold t [--eval-samples n]]]
 
 --sh-degree d renders SH bands 0..d of the file's degree only (d = 0: the diffuse colours), in place.
 --transform "AXIS DEG [SCALE]" (a rotation about x, y or z, then a uniform scale) or 16 numbers (a row-major 4x4
@@ -38,6 +39,10 @@ line also gains the counts before cleaning, the number of components found and t
 --mesh-cell-size s simplifies the mesh by vertex clustering on a grid of side s with quadric placement
 (mesh.simplify_mesh, on the device) after the component removal and before --mesh-normals; the JSON line gains the vertex
 and triangle counts before and after and the time of the call.
+--eval-points gt.ply --eval-threshold t scores the mesh that was just written against a ground-truth point cloud (a PLY
+with x y z; scene_io.load_points_ply): --eval-samples n (default 1 000 000) stratified surface samples of the mesh
+(mesh_eval.evaluate_mesh, on the device), their nearest ground-truth points and the reverse; the JSON line gains accuracy,
+completeness, the Chamfer distance, precision, recall and F-score at the threshold, and the time of the call.
 --coded (with --sh-codes) also renders the quantised scene straight from its codebook (render_compressed: no decoded
 feature tensor) and adds the PSNR of that render against the decoded one (null when they are identical) and the median
 frame time of both, after one warm-up pass each.
@@ -123,7 +128,7 @@ def coverage_report(gaussians, cameras, config):
 
 
 def mesh_report(gaussians, cameras, config, path, voxel_size, bounds, min_component_faces=1, keep_components=None,
-                mesh_normals=False, mesh_cell_size=None):
+                mesh_normals=False, mesh_cell_size=None, eval_points=None, eval_threshold=None, eval_samples=1_000_000):
   """fuse_scene over ``cameras`` + extract_mesh + save_mesh_ply: dims, counts, seconds, vertex distances from the orbit centre"""
   from taichi_splatting_amd import TSDFVolume, fuse_scene, save_mesh_ply
   if bounds is None:
@@ -177,6 +182,19 @@ def mesh_report(gaussians, cameras, config, path, voxel_size, bounds, min_compon
     report['simplification'] = simplification
   if mesh_normals:
     report['normals'] = True
+  if eval_points is not None:
+    from dataclasses import asdict
+    from taichi_splatting_amd import evaluate_mesh, load_points_ply
+    reference = load_points_ply(eval_points, device=mesh.vertices.device)[0]
+    torch.cuda.synchronize()
+    eval_start = time.perf_counter()
+    metrics = evaluate_mesh(mesh, reference, eval_threshold, n=eval_samples)
+    report['evaluation'] = dict(points=str(eval_points), reference_points=int(reference.shape[0]), samples=eval_samples,
+                                threshold=eval_threshold, **{k: round(v, 6) for k, v in asdict(metrics).items()},
+                                eval_s=round(time.perf_counter() - eval_start, 4))
+    print(f"evaluation against {reference.shape[0]} points of {eval_points} with {eval_samples} samples: accuracy "
+          f"{metrics.accuracy:.6f}, completeness {metrics.completeness:.6f}, chamfer {metrics.chamfer:.6f}; at {eval_threshold}: "
+          f"precision {metrics.precision:.4f}, recall {metrics.recall:.4f}, F-score {metrics.fscore:.4f}", file=sys.stderr, flush=True)
   print(f"mesh: {dims[0]} x {dims[1]} x {dims[2]} samples of {voxel_size}; {report['vertices']} vertices, {report['triangles']} "
         f"triangles -> {path}; fusion of {len(cameras)} views {fuse_s:.3f} s, extraction {extract_s:.3f} s; vertex distance from the "
         f"orbit centre median / min / max {report['distance_from_centre']}", file=sys.stderr, flush=True)
@@ -271,6 +289,11 @@ def main():
   p.add_argument('--mesh-cell-size', type=float, default=None, metavar='s',
                  help="simplify the --mesh mesh by vertex clustering on a grid of side s (default: not simplified)")
   p.add_argument('--mesh-normals', action='store_true', help="write area-weighted vertex normals into the --mesh file")
+  p.add_argument('--eval-points', default=None, metavar='gt.ply',
+                 help="score the --mesh mesh against this ground-truth point cloud (needs --eval-threshold)")
+  p.add_argument('--eval-threshold', type=float, default=None, metavar='t',
+                 help="distance within which a point counts for precision / recall / F-score")
+  p.add_argument('--eval-samples', type=int, default=1_000_000, metavar='n', help="surface samples of the mesh (default 1 000 000)")
   p.add_argument('--bounds', type=float, nargs=6, default=None, metavar=('x0', 'y0', 'z0', 'x1', 'y1', 'z1'),
                  help="box of the --mesh volume (default: the box of the gaussians' positions)")
   args = p.parse_args()
@@ -283,6 +306,8 @@ def main():
     sys.exit("render_scene: --min-component-faces and --keep-components must be at least 1")
   if args.voxel_size is not None and not args.voxel_size > 0:
     sys.exit("render_scene: --voxel-size must be positive")
+  if (args.eval_points is None) != (args.eval_threshold is None) or (args.eval_points is not None and args.mesh is None):
+    sys.exit("render_scene: --eval-points and --eval-threshold go together, and need --mesh")
   if args.mesh is not None and args.sh_degree is not None:
     sys.exit("render_scene: --mesh fuses the scene with every stored band: it does not combine with --sh-degree")
   if args.coded and args.sh_codes is None:
@@ -350,7 +375,8 @@ def main():
   if args.mesh is not None:
     try:
       mesh = mesh_report(gaussians, cameras, config, args.mesh, args.voxel_size, args.bounds, args.min_component_faces,
-                         args.keep_components, args.mesh_normals, args.mesh_cell_size)
+                         args.keep_components, args.mesh_normals, args.mesh_cell_size, args.eval_points, args.eval_threshold,
+                         args.eval_samples)
     except ValueError as e:
       sys.exit(f"render_scene: --mesh: {e}")
   print(json.dumps(dict(
